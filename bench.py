@@ -17,14 +17,27 @@ Extra objects on the JSON line:
                 bytes per launch (PMC), `hbm_measured_frac` its rate over
                 8 TB/s; `alg_model` = SURVEY §8(d)'s algorithmic-bytes model
                 (above the HBM peak by construction: D lives in LDS/VGPRs).
-  cpu_baseline  the NumPy CPU port (oracle/rhmc_ref.py) on all the host CPU the
-                job may use (affinity mask, capped by the cgroup CPU quota),
-                one chain per worker process, ~10 s per worker (rank 0, N=1).
-  end_to_end    (leapfrog mode, N=1) the host-buffer C-ABI call rhmc_leapfrog
-                on the same chains: H2D + fused launch + D2H, synchronous — the
-                PCIe-inclusive rate a NumPy caller sees; never `value`.
+  cpu_baseline  (--full) the NumPy CPU port (oracle/rhmc_ref.py) on all the host
+                CPU the job may use (affinity mask, capped by the cgroup CPU
+                quota), one chain per worker process, ~10 s per worker (rank 0,
+                N=1).
+  end_to_end    (--full; leapfrog mode, N=1) the host-buffer C-ABI call
+                rhmc_leapfrog on the same chains: H2D + fused launch + D2H,
+                synchronous — the PCIe-inclusive rate a NumPy caller sees;
+                never `value`.
+
+A run without --full does only what `value` needs: set up, warm up, time the
+--steps launches, print the line.  --full adds the two measurements above
+(--no-cpu / --no-e2e drop one of them again).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2]
+                       [--full] [--dump-outputs DIR]
+  --dump-outputs DIR: after the timed steps, write the arrays the last launch
+  left for its caller (chain states q, p, per-chain iteration counts and
+  status; mh: q and the accept decisions; datagen: the images; rj: the last
+  run's records) as DIR/<name>.npy, float64, at most 64 MB in all (beyond
+  that a fixed seeded sample over the chains).  The inputs are seeded, so two
+  runs with the same arguments start from identical states.
   N > 1 without WORLD_SIZE in the environment: this process starts N rank
   processes of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rank r on
   GPU r) before touching a GPU, relays rank 0's JSON line and fails if any
@@ -248,6 +261,34 @@ def load_pmc(workload, n_chains=None, root=ROOT):
     return pmc, pmc.get("src_hash") != source_hash(root)
 
 
+DUMP_BUDGET_BYTES = 60 << 20    # --dump-outputs: the files of all ranks stay under 64 MB
+
+
+def dump_outputs(directory, arrays, rank=0, world=1):
+    """--dump-outputs: write what the timed path left after its last step as
+    DIR/<name>.npy (rank r > 0: DIR/<name>.rank<r>.npy), float64 (float32
+    arrays stay float32; integer and bool arrays are exact in float64).
+    `arrays` maps a name to (array, axis).  When everything together is over
+    this rank's share of the budget (1 / world), each array keeps a fixed
+    sample along its axis (the chain axis): the same sorted indices
+    (RandomState(0)) on every run, the same fraction of every array."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: (np.asarray(a), ax) for k, (a, ax) in arrays.items()}
+    arrays = {k: (a if a.dtype == np.float32 else a.astype(np.float64), ax)
+              for k, (a, ax) in arrays.items()}
+    total = sum(a.nbytes for a, _ in arrays.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES // world / max(total, 1))
+    for name, (a, ax) in arrays.items():
+        if frac < 1.0:
+            n = a.shape[ax]
+            keep = np.sort(np.random.RandomState(0).choice(n, max(1, int(n * frac)),
+                                                           replace=False))
+            a = np.take(a, keep, axis=ax)
+        suffix = "" if rank == 0 else ".rank%d" % rank
+        np.save(os.path.join(directory, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def bench_datagen(args, wl, P, ctx, dev, stream, world, rank):
     """--mode datagen: n_real Poisson realisations of the workload's true model
     image per launch (gen_noise_profile's inner loop, sampler_RHMC.py:130-133).
@@ -285,6 +326,8 @@ def bench_datagen(args, wl, P, ctx, dev, stream, world, rank):
         dist.barrier()
         wall = shard.max_over_ranks(wall)
     launch_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"images": (out.cpu().numpy(), 0)}, rank, world)
     draws = n_real * rows * cols
     achieved = 8.0 * draws / (launch_ms * 1e-3) / 1e9
     res = {
@@ -381,6 +424,12 @@ def bench_rj(args, wl, gpu, world, rank):
         dist.barrier()
         wall = shard.max_over_ranks(wall)
         steps = int(shard.sum_over_ranks(steps))
+    if args.dump_outputs:
+        # the last run's records, [iteration, chain, ...]: sampled over the chains
+        dump_outputs(args.dump_outputs,
+                     {k: (getattr(g, k), 1) for k in ("q_chain", "p_chain", "E_chain", "V_chain",
+                                                      "T_chain", "A_chain", "move_chain",
+                                                      "N_chain")}, rank, world)
     res = {
         "metric": "chain-leapfrog-steps/sec, reversible-jump run_RHMC (%s %dx%d, K0=%d, "
                   "%d chains/GPU)" % (name, D.shape[0], D.shape[1], K0, n_chains),
@@ -423,9 +472,18 @@ def main():
     ap.add_argument("--global-chains", type=int, default=None,
                     help="total chains split over the ranks (strong scaling, e.g. C4 = 2^20)")
     ap.add_argument("--leap", type=int, default=None, help="leapfrog steps per launch")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure: the NumPy "
+                         "CPU baseline (cpu_baseline) and the host-buffer rhmc_leapfrog rate "
+                         "(end_to_end); a run without it sets up, warms up, times the steps "
+                         "and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left (the arrays "
+                         "a caller of the timed path receives) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the host-buffer (rhmc_leapfrog, PCIe-inclusive) measurement")
+                    help="--full without the host-buffer (rhmc_leapfrog, PCIe-inclusive) "
+                         "measurement")
     ap.add_argument("--mode", choices=("leapfrog", "mh", "integrate", "hmc_random", "datagen",
                                        "rj"),
                     default="leapfrog",
@@ -514,7 +572,7 @@ def main():
         return dry_run(args, wl, world, rank, gpu, total_chains)
     # CPU baseline first: forked workers must not inherit an initialised GPU.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and args.mode == "leapfrog":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.mode == "leapfrog":
         cpu = cpu_baseline(wl)
 
     import torch
@@ -635,6 +693,17 @@ def main():
                 "near_wall_chains": int(((stat & capi.STATUS_NEAR_WALL) != 0).sum()),
                 "near_wall_frac": float(((stat & capi.STATUS_NEAR_WALL) != 0).mean())}
 
+    if args.dump_outputs:
+        # the chain states after the last timed launch and what it reported
+        outs = {"q": (q.cpu().numpy(), 0), "status": (stat, 0)}
+        if args.mode == "mh":
+            outs["mh_accept"] = (mh_acc.cpu().numpy(), 1)
+        else:
+            outs["p"] = (p.cpu().numpy(), 0)
+        if args.mode == "leapfrog":
+            outs["iters"] = (iters, 0)
+        dump_outputs(args.dump_outputs, outs, rank, world)
+
     chain_steps = wl.n_chains * steps_per_launch
     value = total_chains * steps_per_launch * args.steps / wall
     # PMC summaries describe the implicit leapfrog kernel only
@@ -681,7 +750,7 @@ def main():
         # the same hash pmc_summary.py stores; the GPU box has no .git)
         "sources": source_hash(),
     }
-    if args.mode == "leapfrog" and not args.no_e2e and world == 1:
+    if args.full and args.mode == "leapfrog" and not args.no_e2e and world == 1:
         out["end_to_end"] = end_to_end(ctx, P, q, p, wl, leap)
     if args.tables:
         out["config"]["tables"] = args.tables

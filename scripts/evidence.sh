@@ -23,12 +23,12 @@ mkdir -p "$O"
 
 # name -> bench arguments
 declare -A LINE=(
-  [c2]=""
-  [c1]="--workload C1 --no-cpu"
-  [c3]="--workload C3 --no-cpu"
-  [c4]="--workload C4 --no-cpu"
+  [c2]="--full"
+  [c1]="--workload C1 --full --no-cpu"
+  [c3]="--workload C3 --full --no-cpu"
+  [c4]="--workload C4 --full --no-cpu"
   [c4_shard]="--workload C4 --chains 131072 --no-cpu --no-e2e"
-  [c5]="--workload C5 --no-cpu --steps 5 --warmup 1"
+  [c5]="--workload C5 --full --no-cpu --steps 5 --warmup 1"
   [c5_shard]="--workload C5 --chains 1024 --no-cpu --no-e2e --steps 5 --warmup 1"
   [b4]="--workload B4 --no-cpu --no-e2e"
   [b3]="--workload B3 --no-cpu --no-e2e --steps 5 --warmup 1"

@@ -20,7 +20,7 @@ if [ "$MODE" = all ] || [ "$MODE" = test ]; then
   step 1000 pytest_gpu python3 -u -m pytest tests -m gpu -v -rf --timeout 120 --timeout-method thread
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  step 600 bench python3 bench.py
+  step 600 bench python3 bench.py --full
   step 300 bench_2ranks env RHMC_BENCH_DEVICE=0 python3 bench.py --gpus 2 --no-cpu --steps 10
   step 600 rocprof rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --no-cpu
 fi

@@ -76,6 +76,35 @@ def test_gpus_disagreeing_with_world_size_fails():
     assert "disagrees with WORLD_SIZE" in out.stderr
 
 
+def test_dump_outputs_sample_is_fixed_and_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files; over the budget every array keeps the
+    same seeded rows of its chain axis, the same ones on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.RandomState(3)
+    q = rng.standard_normal((1000, 6))
+    acc = rng.randint(0, 2, size=(5, 1000)).astype(np.int32)
+    st = np.arange(1000, dtype=np.int32)
+    arrays = {"q": (q, 0), "mh_accept": (acc, 1), "status": (st, 0)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in arrays}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["q"], q) and np.array_equal(got["mh_accept"], acc)
+    assert np.array_equal(got["status"], st)
+    total = sum(a.nbytes for a in got.values())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", total // 4)
+    bench.dump_outputs(str(tmp_path / "s1"), arrays)
+    bench.dump_outputs(str(tmp_path / "s2"), arrays, rank=1)
+    s1 = {k: np.load(tmp_path / "s1" / (k + ".npy")) for k in arrays}
+    s2 = {k: np.load(tmp_path / "s2" / (k + ".rank1.npy")) for k in arrays}
+    assert all(np.array_equal(s1[k], s2[k]) for k in arrays)
+    assert sum(a.nbytes for a in s1.values()) <= total // 4
+    rows = s1["status"].astype(int)                 # status = the row numbers kept
+    assert len(rows) == 250 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(s1["q"], q[rows]) and np.array_equal(s1["mh_accept"], acc[:, rows])
+
+
 def test_failing_rank_fails_the_launch():
     """A rank that dies makes the launcher exit non-zero (and stop the rest)."""
     out = _bench(["--gpus", "2", "--dry-run", "--workload", "nope"])

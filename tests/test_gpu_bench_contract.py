@@ -14,7 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    out = subprocess.run([sys.executable, "bench.py", "--no-cpu", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu", "--steps", "2",
+                          "--warmup", "1"],
                          cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -46,6 +47,45 @@ def test_bench_json_line():
     sys.path.insert(0, ROOT)
     import bench
     assert d["sources"] == bench.source_hash()    # the line names the sources it ran
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path, gpu_lib):
+    """Without --full the line carries the headline figure and neither of the
+    measurements beside it; --dump-outputs writes the chain states the last
+    timed launch left.  The inputs are seeded, so the dumped states equal
+    warmup + steps = 3 launches of 500 steps from workloads.make("C2") through
+    the host-buffer entry point (the same kernel on the same chains)."""
+    import numpy as np
+    from rhmc_amd import workloads
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "dump")],
+                         cwd=ROOT, capture_output=True, text=True, timeout=110)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("chain-leapfrog-steps/sec, 48x48 1-star 4096 chains")
+    assert d["unit"] == "chain-leapfrog-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 1e8 and d["ms_per_step"] > 0
+    # value = chains x steps per launch / the time of one step
+    assert d["value"] == pytest.approx(4096 * 500 / (d["ms_per_step"] * 1e-3))
+    assert "end_to_end" not in d and d["cpu_baseline"] is None
+    assert sorted(os.listdir(tmp_path / "dump")) == ["iters.npy", "p.npy", "q.npy", "status.npy"]
+    got = {k: np.load(tmp_path / "dump" / (k + ".npy")) for k in ("q", "p", "iters", "status")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["q"].shape == got["p"].shape == (4096, 3)
+    assert got["iters"].shape == (4096, 2) and got["status"].shape == (4096,)
+    wl = workloads.make("C2")
+    ctx = gpu_lib.Context(wl.D, device=0)
+    P = gpu_lib.make_params(**wl.params)
+    q, p = wl.q0, wl.p0
+    for _ in range(3):
+        q, p, it, st = ctx.leapfrog(P, q, p, 500, return_info=True)
+    ctx.close()
+    assert np.array_equal(got["q"], q) and np.array_equal(got["p"], p)
+    assert np.array_equal(got["iters"], it)
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 // rhmc_dense.hpp — the gradient and potential of MANY stars on a SMALL image
 // (32 or 48 px; the reference's own many-star drivers: RHMC-big-sim3.py,
 // K = 100, and RHMC-big-sim4.py, K up to N_max = 120, both on 32x32), for the
-// slotted one-wave-per-chain kernels of rhmc_kernels.hip (star 64 s + lane in
+// slotted one-wave-per-chain kernels of rhmc_perwave.hpp (star 64 s + lane in
 // register slot s, K <= 256).
 //
 // On such an image every star's window covers most of the image, so the

@@ -7,8 +7,8 @@
 // B3's two-slot dense kernel 14.9 -> 22.4 ms and the other families 1-2 %
 // slower, so only these two instantiations take it.  Scheduling does not
 // change the arithmetic: results are bit-identical to the default build.
-#define RHMC_KERNELS_ONLY
-#include "rhmc_kernels.hip"
+#include "rhmc_dense.hpp"    // the gradient policy DenseG
+#include "rhmc_perwave.hpp"  // leapfrog_win_kernel
 
 namespace rhmc {
 template __global__ void leapfrog_win_kernel<DenseG<32>, 1>(LeapArgs);

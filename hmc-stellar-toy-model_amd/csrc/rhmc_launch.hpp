@@ -1,0 +1,1080 @@
+// rhmc_launch.hpp — the host side between the C-ABI (rhmc_kernels.hip) and
+// the kernels: one builder per kernel-argument struct, one launcher per
+// kernel family, and the launch_* function of every operation, which asks
+// rhmc_select.hpp for a Plan and switches on it.  Included by rhmc_kernels.hip
+// alone, after rhmc_ctx, fail() and HIP_TRY: template kernels are launched
+// from the translation unit that instantiates them.
+#pragma once
+
+namespace {
+
+SelectIn select_in(const rhmc_ctx* ctx) {
+  return SelectIn{ctx->rows,  ctx->cols,   ctx->img_f32,  ctx->max_lds,
+                  ctx->n_cu,  ctx->kernel, ctx->mh_fused, ctx->window_split};
+}
+
+// The plan of one call; an unsupported configuration is the error here.
+int plan_for(const rhmc_ctx* ctx, const Consts& c, Op op, int K, int64_t n, Plan* pl) {
+  *pl = select(select_in(ctx), c.use_Vc, c.inv_two_sig2, op, K, n);
+  return pl->family == Family::Unsupported ? fail(RHMC_ERR_UNSUPPORTED, pl->message) : RHMC_OK;
+}
+
+int launch_status() {
+  HIP_TRY(hipGetLastError());
+  return RHMC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Device buffers the context keeps
+// ---------------------------------------------------------------------------
+
+// Grow a device buffer to `need` bytes (contents are not kept).  A failed
+// allocation returns RHMC_ERR_NOMEM without a message: the caller names the buffer.
+int grow(void** ptr, size_t* bytes, size_t need) {
+  if (need <= *bytes) return RHMC_OK;
+  if (*ptr) HIP_TRY(hipFree(*ptr));
+  *ptr = nullptr;
+  *bytes = 0;
+  if (hipMalloc(ptr, need) != hipSuccess) return RHMC_ERR_NOMEM;
+  *bytes = need;
+  return RHMC_OK;
+}
+
+int ensure_scratch(rhmc_ctx* ctx, size_t bytes) {
+  const int rc = grow(&ctx->scratch, &ctx->scratch_bytes, bytes);
+  if (rc == RHMC_ERR_NOMEM)
+    return fail(RHMC_ERR_NOMEM, "hipMalloc scratch " + std::to_string(bytes) + " B failed");
+  return rc;
+}
+
+int ensure_mh_scratch(rhmc_ctx* ctx, size_t bytes) {
+  const int rc = grow(&ctx->mh_scratch, &ctx->mh_scratch_bytes, bytes);
+  return rc == RHMC_ERR_NOMEM ? fail(RHMC_ERR_NOMEM, "hipMalloc MH scratch failed") : rc;
+}
+
+// WinGG's per-chain factor tables (from kWinGlobalFromK stars): one buffer per
+// (context, stream), grown on demand and kept until rhmc_ctx_destroy.  Launches
+// on one stream run in order, so they can share it.  The caller keeps `lease`
+// alive until its launch is enqueued: a grow by another thread on the same
+// stream then replaces the context's buffer, and the old one is released only
+// when its last lease goes (after a sync of its stream).  Every region a launch
+// uses is written by that launch before it is read (win_build_tables,
+// win_build_ey), which RHMC_TABLES_POISON checks.
+using TableLease = std::shared_ptr<rhmc_ctx::TabBuf>;
+
+int work_tables(const rhmc_ctx* ctx, int path, int K, int64_t n, hipStream_t st,
+                double** out, TableLease* lease) {
+  *out = nullptr;
+  lease->reset();
+  if (path != 0 || K < kWinGlobalFromK || n <= 0) return RHMC_OK;
+  const size_t bytes = (size_t)n * WinGG::work_doubles(K) * sizeof(double);
+  const int mode = ctx->table_mode;
+  const bool poison = mode == RHMC_TABLES_STREAM_POISON || mode == RHMC_TABLES_POOL_POISON;
+  if (mode == RHMC_TABLES_POOL || mode == RHMC_TABLES_POOL_POISON ||
+      mode == RHMC_TABLES_POOL_KEEP || mode == RHMC_TABLES_POOL_SYNCFREE ||
+      mode == RHMC_TABLES_POOL_BARRIER) {
+    // Diagnostic: round 5's first scheme, one stream-ordered pool allocation
+    // per launch, released behind it (~TabBuf: hipFreeAsync on st).
+    auto b = std::make_shared<rhmc_ctx::TabBuf>();
+    b->s = st;
+    b->pooled = true;
+    b->sync_free = mode == RHMC_TABLES_POOL_SYNCFREE;
+    if (hipMallocAsync(&b->p, bytes, st) != hipSuccess) {
+      b->p = nullptr;
+      return fail(RHMC_ERR_NOMEM, "hipMallocAsync of " + std::to_string(bytes) +
+                                      " B of windowed factor tables failed");
+    }
+    b->bytes = bytes;
+    if (poison) HIP_TRY(hipMemsetAsync(b->p, 0xFF, bytes, st));
+    if (mode == RHMC_TABLES_POOL_BARRIER) {  // the launch waits for everything before it
+      hipEvent_t e;
+      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      HIP_TRY(hipEventRecord(e, st));
+      HIP_TRY(hipStreamWaitEvent(st, e, 0));
+      HIP_TRY(hipEventDestroy(e));
+    }
+    *out = (double*)b->p;
+    if (mode == RHMC_TABLES_POOL_KEEP) {  // never reused: released at rhmc_ctx_destroy
+      std::lock_guard<std::mutex> lk(ctx->tab_mu);
+      ctx->kept.push_back(b);
+    }
+    *lease = std::move(b);
+    return RHMC_OK;
+  }
+  std::lock_guard<std::mutex> lk(ctx->tab_mu);
+  rhmc_ctx::StreamTables* t = nullptr;
+  for (auto& e : ctx->tabs)
+    if (e.s == st) t = &e;
+  if (!t || !t->buf || t->buf->bytes < bytes) {
+    auto b = std::make_shared<rhmc_ctx::TabBuf>();
+    b->s = st;
+    if (hipMalloc(&b->p, bytes) != hipSuccess) {
+      b->p = nullptr;
+      return fail(RHMC_ERR_NOMEM, "hipMalloc of " + std::to_string(bytes) +
+                                      " B of windowed factor tables failed");
+    }
+    b->bytes = bytes;
+    if (t)
+      t->buf = std::move(b);  // the old buffer goes with its last lease
+    else
+      ctx->tabs.push_back({st, std::move(b)});
+    t = nullptr;
+    for (auto& e : ctx->tabs)
+      if (e.s == st) t = &e;
+  }
+  // 0xFF bytes are NaN doubles: a read of an entry this launch did not write
+  // turns its chain's result NaN (status NONFINITE) instead of reusing a
+  // previous launch's value.
+  if (poison) HIP_TRY(hipMemsetAsync(t->buf->p, 0xFF, bytes, st));
+  *out = (double*)t->buf->p;
+  *lease = t->buf;
+  return RHMC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Kernel arguments: one builder per struct
+// ---------------------------------------------------------------------------
+
+Geometry make_geometry(int rows, int cols) {
+  const int npix = rows * cols;
+  return Geometry{rows, cols, npix, /*npl*/ (npix + kWave - 1) / kWave, /*di*/ kWave / cols,
+                  /*dj*/ kWave % cols, /*work*/ nullptr};
+}
+
+int make_consts(const rhmc_params* P, Consts* c) {
+  if (!P) return fail(RHMC_ERR_ARG, "params is NULL");
+  if (P->reserved != 0) return fail(RHMC_ERR_ARG, "params.reserved must be 0");
+  std::memset(c, 0, sizeof(*c));
+  c->dt = P->dt;
+  c->hdt = P->dt / 2.0;
+  c->delta = P->delta;
+  c->B = P->B_count;
+  c->f_lim = P->f_lim;
+  c->f_low = P->f_low;
+  const double sigma = P->fwhm_pix / 2.354;  // utils.py:480
+  c->two_sig2 = 2 * (sigma * sigma);         // 2*sigma**2 (:484)
+  c->psf_norm = (M_PI * 2) * (sigma * sigma);
+  const double sv = P->fwhm_pix / 2.354;
+  c->var = sv * sv;  // (PSF_FWHM_pix/2.354)**2 (sampler_RHMC.py:384)
+  c->g_xx = P->g_xx;
+  c->g_ff = P->g_ff;
+  c->g_ff2 = P->g_ff2;
+  c->g0 = P->g0;
+  c->g1 = P->g1;
+  c->g2 = P->g2;
+  c->c0 = (P->B_count / P->g0) / P->g_ff;
+  c->alpha = P->alpha;
+  c->beta = P->beta;
+  c->vc_pow = P->Vc_r_pow;
+  c->vprior = P->V_prior_const;
+  c->inv_gff2 = 1.0 / c->g_ff2;
+  c->inv_g1 = 1.0 / c->g1;
+  c->Bg2 = c->B / c->g2;
+  c->two_Bg2 = 2.0 * c->Bg2;
+  c->inv_gxx = 1.0 / c->g_xx;
+  c->inv_two_sig2 = 1.0 / c->two_sig2;
+  c->inv_norm = 1.0 / c->psf_norm;
+  c->inv_var = 1.0 / c->var;
+  {  // PSF factor recurrences of the register-window kernels (rhmc_tiledr.hpp)
+    const double ci = c->inv_two_sig2;
+    c->k_row = std::exp(-2.0 * ci);
+    c->k_col4 = std::exp(-32.0 * ci);
+    // |v0| < rec_vmax keeps every base exp above the fp64 normal range
+    // (c v0^2 < 700) and every ratio below e^700 over up to 8 rows (row
+    // ratios: c (2 (|v0| + 8) + 1) < 700) or 8 columns 4 apart (column
+    // ratios: c (8 (|w0| + 32) + 16) < 700); outside it the direct factors run
+    double vm = std::sqrt(700.0 / ci);
+    vm = std::fmin(vm, (700.0 / ci - 17.0) / 2.0);
+    vm = std::fmin(vm, 700.0 / (8.0 * ci) - 34.0);
+    c->rec_vmax = (ci > 0.0 && vm > 0.0) ? vm : 0.0;
+  }
+  c->near_f = P->f_lim - 0x1p-40 * std::fmax(1.0, std::fabs(P->f_lim));
+  c->counter_max = P->counter_max;
+  c->use_prior = P->use_prior != 0;
+  c->use_Vc = P->use_Vc != 0;
+  return RHMC_OK;
+}
+
+// One-star kernels (register-window, lane-group); the launcher sets Df.
+LeapArgsK1 k1_args(const rhmc_ctx* ctx, const Consts& c, double* q, double* p, int32_t* it,
+                   int32_t* st, int64_t n, int n_steps) {
+  return LeapArgsK1{q, p, it, st, ctx->d_D, /*Df*/ nullptr, n, n_steps, ctx->rows, ctx->cols,
+                    /*pad*/ 0, c};
+}
+
+// Multi-star register kernels (pixel-major, register-window); the launcher
+// sets Df.  dtv / steps: HMC_random only.
+LeapArgsKR kr_args(const rhmc_ctx* ctx, const Consts& c, double* q, double* p, int32_t* it,
+                   int32_t* st, int64_t n, int K, int n_steps, const double* dtv = nullptr,
+                   const int32_t* steps = nullptr) {
+  return LeapArgsKR{q, p, it, st, ctx->d_D, /*Df*/ nullptr, n, K, n_steps, /*side*/ ctx->rows,
+                    /*pad*/ 0, c, dtv, steps};
+}
+
+// One-wave-per-chain kernels (LDS-image, slotted).
+LeapArgs leap_args(const rhmc_ctx* ctx, const Consts& c, double* q, double* p, int32_t* it,
+                   int32_t* st, int64_t n, int K, int n_steps) {
+  return LeapArgs{q, p, it, st, ctx->d_D, n, K, n_steps, make_geometry(ctx->rows, ctx->cols), c};
+}
+
+EnergyArgs energy_args(const rhmc_ctx* ctx, const Consts& c, const double* q, const double* p,
+                       double* V, double* T, int64_t n, int K, int f_pos) {
+  return EnergyArgs{q, p, V, T, ctx->d_D, n, K, f_pos & (RHMC_V_FLUX_WALL | RHMC_V_NO_POSCHECK),
+                    make_geometry(ctx->rows, ctx->cols), c};
+}
+
+// A ragged set's rows and star counts (LeapArgs, LeapArgsKR, EnergyArgs).
+template <class A>
+void set_ragged(A& a, const int32_t* d_K, const int64_t* d_rows, int64_t ld) {
+  a.Kc = d_K;
+  a.rows = d_rows;
+  a.ld = ld;
+}
+
+// The MH kernels' record pointers (MhArgs, MhK1Args, MhKArgs); rec nullable.
+template <class A>
+void set_record(A& k, const rhmc_mh_record* rec) {
+  k.q_chain = rec ? rec->q_chain : nullptr;
+  k.E_chain = rec ? rec->E_chain : nullptr;
+  k.V_chain = rec ? rec->V_chain : nullptr;
+  k.T_chain = rec ? rec->T_chain : nullptr;
+  k.accept = rec ? rec->accept : nullptr;
+}
+
+// ---------------------------------------------------------------------------
+// Run-time value -> template argument, each switch written once
+// ---------------------------------------------------------------------------
+template <class T> struct TypeTag { using type = T; };
+template <int N> struct IntTag { static constexpr int value = N; };
+
+// The explicit integrators (launch_integrate has checked the range).
+template <class F>
+int with_solver(int32_t solver, F&& f) {
+  if (solver == RHMC_SOLVER_HMC) return f(IntTag<RHMC_SOLVER_HMC>{});
+  if (solver == RHMC_SOLVER_RHMC_NAIVE) return f(IntTag<RHMC_SOLVER_RHMC_NAIVE>{});
+  return f(IntTag<RHMC_SOLVER_RHMC_LEAPFROG>{});
+}
+
+// Image sides: the pixel-major and dense kernels are built for 32/48 px, the
+// one-star kernels for 32/48/64, the implicit one-star step for 96/128 too.
+// The plan has checked that the side is one of them.
+template <class F>
+int with_side2(int side, F&& f) {
+  return side == 32 ? f(IntTag<32>{}) : f(IntTag<48>{});
+}
+template <class F>
+int with_side3(int side, F&& f) {
+  switch (side) {
+    case 32: return f(IntTag<32>{});
+    case 48: return f(IntTag<48>{});
+    default: return f(IntTag<64>{});
+  }
+}
+template <class F>
+int with_side5(int side, F&& f) {
+  switch (side) {
+    case 96: return f(IntTag<96>{});
+    case 128: return f(IntTag<128>{});
+    default: return with_side3(side, f);
+  }
+}
+
+// The slotted one-wave-per-chain kernels run one of two gradient policies:
+// WinG (windowed tables, any square image; needs window_exact) or DenseG<IMG>
+// (rhmc_dense.hpp, 32/48-px images: full-image pixel-major Lambda, star-major
+// sums).  A "path" names it: 0 = windowed, 32 / 48 = dense at that side.
+template <class G, class F>
+int with_slots(int K, F&& f) {
+  switch (win_slots(K)) {
+    case 1: return f(TypeTag<G>{}, IntTag<1>{});
+    case 2: return f(TypeTag<G>{}, IntTag<2>{});
+    default: return f(TypeTag<G>{}, IntTag<4>{});
+  }
+}
+// K >= kWinGlobalFromK on the windowed path: the global-table policy (the
+// only policy instantiated past 256 stars, 8 or 16 slots)
+template <class F>
+int with_big(int K, F&& f) {
+  if constexpr (kWinGlobalFromK <= 64 * 2)
+    if (K <= 128) return f(TypeTag<WinGG>{}, IntTag<2>{});
+  if constexpr (kWinGlobalFromK <= 64 * 4)
+    if (K <= 256) return f(TypeTag<WinGG>{}, IntTag<4>{});
+  if (K <= 512) return f(TypeTag<WinGG>{}, IntTag<8>{});
+  return f(TypeTag<WinGG>{}, IntTag<16>{});
+}
+// LDS-table policies below kWinGlobalFromK (windowed) / 256 (dense)
+template <class G, class F>
+int with_slots_lds(int K, F&& f) {
+  if (K <= 64) return f(TypeTag<G>{}, IntTag<1>{});
+  if constexpr (kWinGlobalFromK > 65 || !std::is_same<G, WinG>::value)
+    if (K <= 128) return f(TypeTag<G>{}, IntTag<2>{});
+  if constexpr (kWinGlobalFromK > 129 || !std::is_same<G, WinG>::value)
+    return f(TypeTag<G>{}, IntTag<4>{});
+  return fail(RHMC_ERR_ARG, "no LDS-table slotted kernel for K = " + std::to_string(K));
+}
+template <class F>
+int with_path(int path, int K, F&& f) {
+  if (path == 32) return with_slots<DenseG<32>>(K, f);  // dense_path: K <= 256
+  if (path == 48) return with_slots<DenseG<48>>(K, f);
+  if (K >= kWinGlobalFromK) return with_big(K, f);
+  return with_slots_lds<WinG>(K, f);
+}
+// The windowed energy kernel's policy: column tables only (WinEG) below
+// kWinGlobalFromK, the global tables from there
+template <class F>
+int with_energy_win(int K, F&& f) {
+  if (K >= kWinGlobalFromK) return with_big(K, f);
+  if (K <= 64) return f(TypeTag<WinEG>{}, IntTag<1>{});
+  if constexpr (kWinGlobalFromK > 65)
+    if (K <= 128) return f(TypeTag<WinEG>{}, IntTag<2>{});
+  if constexpr (kWinGlobalFromK > 129) return f(TypeTag<WinEG>{}, IntTag<4>{});
+  return fail(RHMC_ERR_ARG, "no LDS-table energy kernel for K = " + std::to_string(K));
+}
+
+// ---------------------------------------------------------------------------
+// Slotted kernels: the launch shape, written once
+// ---------------------------------------------------------------------------
+struct SlotShape {
+  dim3 grid, block;
+  size_t lds = 0;
+  TableLease lease;  // held until the launch is enqueued
+};
+
+// W waves per workgroup and the LDS they need.  Windowed: LDS = W * tables
+// (K <= 256: 136 KB for one wave, within gfx950's 160 KB; a device with less
+// LDS gets RHMC_ERR_UNSUPPORTED here, not a failed launch); WinGG: the exp
+// table only; dense: four waves (32 px: 41.5 KB, 48 px: 92.6 KB).
+int pick_waves_slotted(const rhmc_ctx* ctx, const Plan& pl, int K, size_t* lds, int* W) {
+  const size_t max_lds = (size_t)ctx->max_lds;
+  *W = 4;
+  switch (pl.policy) {
+    case Policy::DenseG:
+      *lds = pl.path == 32 ? DenseG<32>::lds_bytes(4) : DenseG<48>::lds_bytes(4);
+      if (*lds > max_lds) return fail(RHMC_ERR_UNSUPPORTED, "dense kernel LDS");
+      return RHMC_OK;
+    case Policy::WinGG:
+      *lds = WinGG::lds_bytes(4, K);
+      return RHMC_OK;
+    case Policy::WinEG:
+      while (*W > 1 && WinEG::lds_bytes(*W, K) > max_lds) *W >>= 1;
+      *lds = WinEG::lds_bytes(*W, K);
+      if (*lds > max_lds)
+        return fail(RHMC_ERR_UNSUPPORTED, "windowed energy tables exceed the device's LDS");
+      return RHMC_OK;
+    case Policy::WinG:
+      break;
+  }
+  while (*W > 1 && WinG::lds_bytes(*W, K) > max_lds) *W >>= 1;
+  *lds = WinG::lds_bytes(*W, K);
+  if (*lds > max_lds)
+    return fail(RHMC_ERR_UNSUPPORTED, "windowed PSF tables for K = " + std::to_string(K) +
+                                          " exceed the device's LDS (" + std::to_string(*lds) +
+                                          " B > " + std::to_string(ctx->max_lds) + " B)");
+  return RHMC_OK;
+}
+
+// Workgroup, WinGG's table lease (into g->work) and the grid of one wave per
+// chain.  set_device: the callers that have not selected the device yet do it
+// between the two, as they always have.
+int slotted_shape(const rhmc_ctx* ctx, const Plan& pl, int K, int64_t n, hipStream_t s,
+                  bool set_device, Geometry* g, SlotShape* sh) {
+  int W;
+  if (int rc = pick_waves_slotted(ctx, pl, K, &sh->lds, &W)) return rc;
+  if (set_device) HIP_TRY(hipSetDevice(ctx->device));
+  if (int rc = work_tables(ctx, pl.path, K, n, s, &g->work, &sh->lease)) return rc;
+  sh->grid = dim3((unsigned)((n + W - 1) / W));
+  sh->block = dim3(W * kWave);
+  return RHMC_OK;
+}
+
+int launch_leap_slotted(const rhmc_ctx* ctx, const Plan& pl, LeapArgs a, hipStream_t s) {
+  SlotShape sh;
+  if (int rc = slotted_shape(ctx, pl, a.K, a.n_chains, s, false, &a.g, &sh)) return rc;
+  return with_path(pl.path, a.K, [&](auto gt, auto st) {
+    using G = typename decltype(gt)::type;
+    hipLaunchKernelGGL((leapfrog_win_kernel<G, decltype(st)::value>), sh.grid, sh.block, sh.lds,
+                       s, a);
+    return launch_status();
+  });
+}
+
+int launch_energy_slotted(const rhmc_ctx* ctx, const Plan& pl, EnergyArgs a, hipStream_t s) {
+  SlotShape sh;
+  if (int rc = slotted_shape(ctx, pl, a.K, a.n_chains, s, false, &a.g, &sh)) return rc;
+  auto go = [&](auto gt, auto st) {
+    using G = typename decltype(gt)::type;
+    hipLaunchKernelGGL((energy_win_kernel<G, decltype(st)::value>), sh.grid, sh.block, sh.lds, s,
+                       a);
+    return launch_status();
+  };
+  return pl.path ? with_path(pl.path, a.K, go) : with_energy_win(a.K, go);
+}
+
+// ---------------------------------------------------------------------------
+// LDS-image kernels
+// ---------------------------------------------------------------------------
+
+// Workgroup shape: W waves share one LDS copy of D; pick the largest W<=4
+// whose LDS fits.
+int pick_waves(const rhmc_ctx* ctx, int K, size_t* lds_bytes, int* W_out) {
+  const size_t img = (size_t)ctx->rows * ctx->cols * sizeof(double);
+  const size_t tab = table_doubles(K, ctx->rows, ctx->cols) * sizeof(double);
+  for (int W = 4; W >= 1; W >>= 1) {
+    const size_t need = img + W * tab;
+    if (need <= (size_t)ctx->max_lds) {
+      *lds_bytes = need;
+      *W_out = W;
+      return RHMC_OK;
+    }
+  }
+  return fail(RHMC_ERR_UNSUPPORTED,
+              "image + PSF tables exceed LDS (" + std::to_string(img + tab) + " B > " +
+                  std::to_string(ctx->max_lds) + " B); large images are not built yet");
+}
+
+// One wave per chain, MAXK register accumulators (the next power of two).
+// go(IntTag<MAXK>, grid, block, lds) enqueues the kernel.
+template <class F>
+int launch_lds_image(const rhmc_ctx* ctx, int K, int64_t n, F&& go) {
+  size_t lds;
+  int W;
+  if (int rc = pick_waves(ctx, K, &lds, &W)) return rc;
+  const dim3 grid((unsigned)((n + W - 1) / W)), block(W * kWave);
+  if (K == 1) go(IntTag<1>{}, grid, block, lds);
+  else if (K <= 2) go(IntTag<2>{}, grid, block, lds);
+  else if (K <= 4) go(IntTag<4>{}, grid, block, lds);
+  else if (K <= 8) go(IntTag<8>{}, grid, block, lds);
+  else go(IntTag<16>{}, grid, block, lds);
+  return launch_status();
+}
+
+int launch_energy_lds_image(const rhmc_ctx* ctx, const EnergyArgs& a, hipStream_t s) {
+  return launch_lds_image(ctx, a.K, a.n_chains, [&](auto mk, dim3 grid, dim3 block, size_t lds) {
+    hipLaunchKernelGGL(energy_kernel<decltype(mk)::value>, grid, block, lds, s, a);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// One-star kernels
+// ---------------------------------------------------------------------------
+
+// Launch shape of a one-star kernel layout TL (TiledR, TiledL): four waves per
+// workgroup, TL::CPW chains per wave, the image in LDS.
+template <class TL>
+int k1_shape(const rhmc_ctx* ctx, int64_t n, dim3* grid, dim3* block, size_t* lds) {
+  *lds = TL::lds_bytes();
+  if (*lds > (size_t)ctx->max_lds) return fail(RHMC_ERR_UNSUPPORTED, "image too large for LDS");
+  constexpr int W = 4;
+  const int64_t waves = (n + TL::CPW - 1) / TL::CPW;
+  *grid = dim3((unsigned)((waves + W - 1) / W));
+  *block = dim3(W * kWave);
+  return RHMC_OK;
+}
+
+// Register-window single-star kernel (rhmc_tiledr.hpp).
+template <int IMG, int WIN, typename DT, bool PROF>
+int launch_tiledr_t(const rhmc_ctx* ctx, const LeapArgsK1& a, hipStream_t s) {
+  dim3 grid, block;
+  size_t lds;
+  if (int rc = k1_shape<TiledR<IMG, WIN, DT>>(ctx, a.n_chains, &grid, &block, &lds)) return rc;
+  hipLaunchKernelGGL((leapfrog_k1_tiledr<IMG, WIN, DT, PROF>), grid, block, lds, s, a);
+  return launch_status();
+}
+// The plan's window (28 px when the PSF allows it) and pixel cache (fp32 when
+// the image allows it exactly).  A library built with -DRHMC_PHASE_PROF (make
+// prof, tools/phase_prof.py only) runs the phase-timing instantiation instead,
+// which writes cycle counts over the state.
+template <int IMG>
+int launch_tiledr(const rhmc_ctx* ctx, const Plan& pl, LeapArgsK1 a, hipStream_t s) {
+  const bool w28 = pl.window == 28;
+  if (pl.f32) a.Df = ctx->d_Df;
+#ifdef RHMC_PHASE_PROF
+  if (w28 && pl.f32) return launch_tiledr_t<IMG, 28, float, true>(ctx, a, s);
+#endif
+  if (pl.f32)
+    return w28 ? launch_tiledr_t<IMG, 28, float, false>(ctx, a, s)
+               : launch_tiledr_t<IMG, 32, float, false>(ctx, a, s);
+  return w28 ? launch_tiledr_t<IMG, 28, double, false>(ctx, a, s)
+             : launch_tiledr_t<IMG, 32, double, false>(ctx, a, s);
+}
+
+// Lane-group single-star kernel for large batches (rhmc_tiledl.hpp).
+template <int IMG, typename DT, int LPC>
+int launch_tiledl_t(const rhmc_ctx* ctx, const LeapArgsK1& a, hipStream_t s) {
+  dim3 grid, block;
+  size_t lds;
+  if (int rc = k1_shape<TiledL<IMG, 28, DT, LPC>>(ctx, a.n_chains, &grid, &block, &lds))
+    return rc;
+  hipLaunchKernelGGL((leapfrog_k1_tiledl<IMG, 28, DT, LPC>), grid, block, lds, s, a);
+  return launch_status();
+}
+template <int IMG>
+int launch_tiledl(const rhmc_ctx* ctx, const Plan& pl, LeapArgsK1 a, hipStream_t s) {
+  if (pl.f32) {
+    a.Df = ctx->d_Df;
+    return pl.lpc == 4 ? launch_tiledl_t<IMG, float, 4>(ctx, a, s)
+                       : launch_tiledl_t<IMG, float, 1>(ctx, a, s);
+  }
+  return pl.lpc == 4 ? launch_tiledl_t<IMG, double, 4>(ctx, a, s)
+                     : launch_tiledl_t<IMG, double, 1>(ctx, a, s);
+}
+
+// The other one-star register-window kernels (explicit integrators,
+// HMC_random, energy, fused MH): 28-px window on a 32/48/64-px image, fp32
+// pixel cache when the image is exact in fp32.  go(IntTag<IMG>, TypeTag<DT>,
+// grid, block, lds) enqueues the kernel; the caller has set Df.
+template <class F>
+int launch_k1_w28(const rhmc_ctx* ctx, bool f32, int64_t n, F&& go) {
+  return with_side3(ctx->rows, [&](auto img) {
+    constexpr int IMG = decltype(img)::value;
+    dim3 grid, block;
+    size_t lds;
+    if (f32) {
+      if (int rc = k1_shape<TiledR<IMG, 28, float>>(ctx, n, &grid, &block, &lds)) return rc;
+      go(img, TypeTag<float>{}, grid, block, lds);
+    } else {
+      if (int rc = k1_shape<TiledR<IMG, 28, double>>(ctx, n, &grid, &block, &lds)) return rc;
+      go(img, TypeTag<double>{}, grid, block, lds);
+    }
+    return launch_status();
+  });
+}
+
+// ---------------------------------------------------------------------------
+// Multi-star register kernels
+// ---------------------------------------------------------------------------
+
+// Multi-star register-window kernel (rhmc_tiledrk.hpp): K in [1, 64], square
+// image of side >= 32, PSF narrow enough for the 28-row window.
+template <typename DT, int SLOTS, bool TAB, int SOLVER, int WS>
+int launch_kr_ws(const rhmc_ctx* ctx, const LeapArgsKR& a, int f_pos, hipStream_t s) {
+  using TK = TiledRK<DT, SLOTS, TAB>;
+  int W = 4;
+  while (W > WS && TK::lds_bytes(W, a.K, a.side, WS) > (size_t)ctx->max_lds / 2) W >>= 1;
+  const size_t lds = TK::lds_bytes(W, a.K, a.side, WS);
+  if (lds > (size_t)ctx->max_lds) return fail(RHMC_ERR_UNSUPPORTED, "factor tables exceed LDS");
+  const int64_t waves = (a.n_chains + TK::CPW - 1) / TK::CPW * WS;
+  const dim3 grid((unsigned)((waves + W - 1) / W)), block(W * kWave);
+  hipLaunchKernelGGL((leapfrog_kr<DT, SLOTS, TAB, SOLVER, WS>), grid, block, lds, s, a, f_pos);
+  return launch_status();
+}
+
+// The window split (waves per chain pair) exists for the implicit step without
+// LDS tables only.
+template <typename DT, int SLOTS, bool TAB, int SOLVER>
+int launch_kr_t(const rhmc_ctx* ctx, const Plan& pl, const LeapArgsKR& a, int f_pos,
+                hipStream_t s) {
+  if constexpr (SOLVER == RHMC_SOLVER_IMPLICIT && !TAB) {
+    switch (pl.split) {
+      case 2: return launch_kr_ws<DT, SLOTS, TAB, SOLVER, 2>(ctx, a, f_pos, s);
+      case 4: return launch_kr_ws<DT, SLOTS, TAB, SOLVER, 4>(ctx, a, f_pos, s);
+      default: break;
+    }
+  }
+  return launch_kr_ws<DT, SLOTS, TAB, SOLVER, 1>(ctx, a, f_pos, s);
+}
+
+template <int SOLVER = RHMC_SOLVER_IMPLICIT>
+int launch_kr(const rhmc_ctx* ctx, const Plan& pl, LeapArgsKR a, int f_pos, hipStream_t s) {
+  if (pl.f32) a.Df = ctx->d_Df;
+  if (pl.tables)
+    return pl.f32 ? launch_kr_t<float, 1, true, SOLVER>(ctx, pl, a, f_pos, s)
+                  : launch_kr_t<double, 1, true, SOLVER>(ctx, pl, a, f_pos, s);
+  if (pl.slots == 1)
+    return pl.f32 ? launch_kr_t<float, 1, false, SOLVER>(ctx, pl, a, f_pos, s)
+                  : launch_kr_t<double, 1, false, SOLVER>(ctx, pl, a, f_pos, s);
+  return pl.f32 ? launch_kr_t<float, 2, false, SOLVER>(ctx, pl, a, f_pos, s)
+                : launch_kr_t<double, 2, false, SOLVER>(ctx, pl, a, f_pos, s);
+}
+
+// Pixel-major multi-star kernel (rhmc_pixk.hpp), 32/48-px fp32-exact images.
+template <int IMG, int SOLVER = RHMC_SOLVER_IMPLICIT, bool RAGGED = false>
+int launch_pk(const rhmc_ctx* ctx, LeapArgsKR a, hipStream_t s, int f_pos = 0) {
+  using PK = PixK<IMG, 10>;  // LDS layout does not depend on the columns per pass
+  int W = 4;
+  while (W > 1 && PK::lds_bytes(W) > (size_t)ctx->max_lds / 2) W >>= 1;
+  const size_t lds = PK::lds_bytes(W);
+  if (lds > (size_t)ctx->max_lds) return fail(RHMC_ERR_UNSUPPORTED, "pixk LDS");
+  a.Df = ctx->d_Df;
+  const int64_t waves = (a.n_chains + PK::CPW - 1) / PK::CPW;
+  const dim3 grid((unsigned)((waves + W - 1) / W)), block(W * kWave);
+  hipLaunchKernelGGL((leapfrog_pk<IMG, 10, SOLVER, RAGGED>), grid, block, lds, s, a, f_pos);
+  return launch_status();
+}
+
+// The multi-star plan (pixel-major or register-window) with integrator SOLVER.
+template <int SOLVER>
+int launch_multi(const rhmc_ctx* ctx, const Plan& pl, const LeapArgsKR& a, int f_pos,
+                 hipStream_t s) {
+  if (pl.family == Family::PixMajor)
+    return with_side2(ctx->rows, [&](auto img) {
+      return launch_pk<decltype(img)::value, SOLVER>(ctx, a, s, f_pos);
+    });
+  return launch_kr<SOLVER>(ctx, pl, a, f_pos, s);
+}
+
+// ---------------------------------------------------------------------------
+// The operations
+// ---------------------------------------------------------------------------
+
+// n_steps implicit steps of n_chains chains on device buffers, async on `s`.
+int launch_leapfrog(rhmc_ctx* ctx, const rhmc_params* P, double* d_q, double* d_p,
+                    int64_t n_chains, int32_t K, int32_t n_steps, int32_t* d_it, int32_t* d_st,
+                    hipStream_t s) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  if (n_steps < 0) return fail(RHMC_ERR_ARG, "n_steps < 0");
+  if (P->counter_max < 1) return fail(RHMC_ERR_ARG, "counter_max < 1");
+  if (n_chains == 0) return RHMC_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  Plan pl;
+  if ((rc = plan_for(ctx, c, Op::Step, K, n_chains, &pl))) return rc;
+  switch (pl.family) {
+    case Family::RegWin1: {
+      const LeapArgsK1 t = k1_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, n_steps);
+      return with_side5(ctx->rows, [&](auto img) {
+        return launch_tiledr<decltype(img)::value>(ctx, pl, t, s);
+      });
+    }
+    case Family::Lane: {
+      const LeapArgsK1 t = k1_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, n_steps);
+      return with_side3(ctx->rows, [&](auto img) {
+        return launch_tiledl<decltype(img)::value>(ctx, pl, t, s);
+      });
+    }
+    case Family::PixMajor:
+    case Family::MultiWin:
+      return launch_multi<RHMC_SOLVER_IMPLICIT>(
+          ctx, pl, kr_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, K, n_steps), 0, s);
+    case Family::Slotted:
+      return launch_leap_slotted(ctx, pl,
+                                 leap_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, K, n_steps), s);
+    default: {
+      const LeapArgs a = leap_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, K, n_steps);
+      return launch_lds_image(ctx, K, n_chains, [&](auto mk, dim3 grid, dim3 block, size_t lds) {
+        hipLaunchKernelGGL(leapfrog_kernel<decltype(mk)::value>, grid, block, lds, s, a);
+      });
+    }
+  }
+}
+
+// V (and optionally T) of n chains on device buffers, async on `s`.
+int launch_energy(const rhmc_ctx* ctx, const Consts& c, const double* d_q, const double* d_p,
+                  double* d_V, double* d_T, int64_t n, int K, int f_pos, hipStream_t s) {
+  Plan pl;
+  if (int rc = plan_for(ctx, c, Op::Energy, K, n, &pl)) return rc;
+  const EnergyArgs a = energy_args(ctx, c, d_q, d_p, d_V, d_T, n, K, f_pos);
+  switch (pl.family) {
+    case Family::RegWin1: {  // rhmc_mhk1.hpp
+      if (n == 0) return RHMC_OK;
+      const EnergyK1Args k{d_q, d_p, d_V, d_T, ctx->d_D, pl.f32 ? ctx->d_Df : nullptr, n, a.f_pos,
+                           /*pad*/ 0, c};
+      return launch_k1_w28(ctx, pl.f32, n,
+                           [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
+        using DT = typename decltype(dt)::type;
+        hipLaunchKernelGGL((energy_k1_tiledr<decltype(img)::value, DT>), grid, block, lds, s, k);
+      });
+    }
+    case Family::Slotted: return launch_energy_slotted(ctx, pl, a, s);
+    default: return launch_energy_lds_image(ctx, a, s);
+  }
+}
+
+// dVdq (kind 0) or dphidq (kind 1) of n chains on device buffers, async on `s`.
+int launch_gradient(const rhmc_ctx* ctx, const Plan& pl, const Consts& c, const double* d_q,
+                    double* d_grad, int64_t n, int K, int kind, hipStream_t s) {
+  GradArgs a{d_q, d_grad, ctx->d_D, n, K, /*with_metric*/ kind,
+             make_geometry(ctx->rows, ctx->cols), c};
+  if (pl.family != Family::Slotted)
+    return launch_lds_image(ctx, K, n, [&](auto mk, dim3 grid, dim3 block, size_t lds) {
+      hipLaunchKernelGGL(gradient_kernel<decltype(mk)::value>, grid, block, lds, s, a);
+    });
+  SlotShape sh;
+  if (int rc = slotted_shape(ctx, pl, K, n, s, false, &a.g, &sh)) return rc;
+  return with_path(pl.path, K, [&](auto gt, auto st) {
+    using G = typename decltype(gt)::type;
+    hipLaunchKernelGGL((gradient_win_kernel<G, decltype(st)::value>), sh.grid, sh.block, sh.lds,
+                       s, a);
+    return launch_status();
+  });
+}
+
+// [K_min, K_max]: one ragged family (rhmc_select.hpp) and one register-slot
+// count (the launch's SLOTS and LDS follow K_max)
+int ragged_check(const rhmc_ctx* ctx, const Consts& c, int K_min, int K_max, int64_t ld) {
+  if (K_min < 1 || K_max > kMaxK || K_min > K_max)
+    return fail(RHMC_ERR_ARG, "ragged set: need 1 <= K_min <= K_max <= 1024");
+  if (win_slots(K_min) != win_slots(K_max))
+    return fail(RHMC_ERR_ARG, "ragged set: K_min and K_max need the same register slots "
+                              "(1-64, 65-128, 129-256, 257-512, 513-1024 stars)");
+  if (ld < 3 * (int64_t)K_max) return fail(RHMC_ERR_ARG, "ragged set: ld < 3 K_max");
+  const SelectIn in = select_in(ctx);
+  const int f = ragged_family(in, c.use_Vc, c.inv_two_sig2, K_min);
+  for (int K = K_min; K <= K_max; ++K)
+    if (ragged_family(in, c.use_Vc, c.inv_two_sig2, K) != f || f == 0)
+      return fail(RHMC_ERR_UNSUPPORTED, "ragged set: K = " + std::to_string(K) +
+                                            " is not served by a slotted kernel on this image "
+                                            "(rhmc_ragged_ok)");
+  return RHMC_OK;
+}
+
+// The step on a ragged set: K_max's plan, which ragged_check has made the
+// plan of every K of the set.
+int launch_leapfrog_ragged(rhmc_ctx* ctx, const rhmc_params* P, double* d_q, double* d_p,
+                           int64_t ld, const int64_t* d_rows, const int32_t* d_K, int64_t n,
+                           int K_min, int K_max, int32_t n_steps, hipStream_t s) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  if (n_steps < 0) return fail(RHMC_ERR_ARG, "n_steps < 0");
+  if (P->counter_max < 1) return fail(RHMC_ERR_ARG, "counter_max < 1");
+  if ((rc = ragged_check(ctx, c, K_min, K_max, ld))) return rc;
+  if (n == 0) return RHMC_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  Plan pl;
+  if ((rc = plan_for(ctx, c, Op::Step, K_max, n, &pl))) return rc;
+  if (pl.family == Family::PixMajor) {  // each chain its own row and K
+    LeapArgsKR t = kr_args(ctx, c, d_q, d_p, nullptr, nullptr, n, K_max, n_steps);
+    set_ragged(t, d_K, d_rows, ld);
+    return with_side2(ctx->rows, [&](auto img) {
+      return launch_pk<decltype(img)::value, RHMC_SOLVER_IMPLICIT, true>(ctx, t, s);
+    });
+  }
+  LeapArgs a = leap_args(ctx, c, d_q, d_p, nullptr, nullptr, n, K_max, n_steps);
+  set_ragged(a, d_K, d_rows, ld);
+  return launch_leap_slotted(ctx, pl, a, s);
+}
+
+int launch_energy_ragged(rhmc_ctx* ctx, const rhmc_params* P, const double* d_q, int64_t ld,
+                         const int64_t* d_rows, const int32_t* d_K, int64_t n, int K_min,
+                         int K_max, int f_pos, double* d_V, hipStream_t s) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  if ((rc = ragged_check(ctx, c, K_min, K_max, ld))) return rc;
+  if (n == 0) return RHMC_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  Plan pl;
+  if ((rc = plan_for(ctx, c, Op::Energy, K_max, n, &pl))) return rc;
+  EnergyArgs a = energy_args(ctx, c, d_q, nullptr, d_V, nullptr, n, K_max, f_pos);
+  set_ragged(a, d_K, d_rows, ld);
+  if (pl.family == Family::LdsImage)  // the pixel-major step's energy
+    return launch_energy_lds_image(ctx, a, s);
+  return launch_energy_slotted(ctx, pl, a, s);
+}
+
+// ---------------------------------------------------------------------------
+// Metropolis-Hastings
+// ---------------------------------------------------------------------------
+
+// The run's parameters at MH iteration l: multi_gym.run_RHMC's schedules
+// (sampler_RHMC.py:1010-1016) set g_ff2 = schedule_g_ff2[l] and beta =
+// schedule_beta[l] while l < the schedule's size and keep the last value
+// after it; no schedule keeps P's value.
+rhmc_params sched_params(const rhmc_params& P, const rhmc_mh_schedule* sc, int l) {
+  rhmc_params q = P;
+  if (sc && sc->g_ff2 && sc->n_g_ff2 > 0) q.g_ff2 = sc->g_ff2[l < sc->n_g_ff2 ? l : sc->n_g_ff2 - 1];
+  if (sc && sc->beta && sc->n_beta > 0) q.beta = sc->beta[l < sc->n_beta ? l : sc->n_beta - 1];
+  return q;
+}
+
+bool sched_active(const rhmc_mh_schedule* sc) {
+  return sc && ((sc->g_ff2 && sc->n_g_ff2 > 0) || (sc->beta && sc->n_beta > 0));
+}
+
+// One star: the whole MH loop in one launch (rhmc_mhk1.hpp).
+int launch_mh_k1(const rhmc_ctx* ctx, const Plan& pl, MhK1Args k, hipStream_t s) {
+  if (pl.f32) k.Df = ctx->d_Df;
+  return launch_k1_w28(ctx, pl.f32, k.n, [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
+    using DT = typename decltype(dt)::type;
+    hipLaunchKernelGGL((mh_k1_tiledr<decltype(img)::value, 28, DT>), grid, block, lds, s, k);
+  });
+}
+
+// V(q) once, then one mh_pk_iter launch per iteration (rhmc_mhpk.hpp); V
+// [n] is the carried V(q) (device scratch).  A schedule changes only g_ff2
+// and beta, which this kernel's V does not read (no repulsion here), so the
+// carried V stays exact; each launch gets its iteration's constants.
+template <int IMG>
+int launch_mh_pk(const rhmc_ctx* ctx, MhKArgs k, double* V, hipStream_t s,
+                 const rhmc_params* P, const rhmc_mh_schedule* sc) {
+  using MP = MhPK<IMG, 10>;
+  int W = 4;
+  while (W > 1 && MP::lds_bytes(W) > (size_t)ctx->max_lds / 2) W >>= 1;
+  const size_t lds = MP::lds_bytes(W);
+  if (lds > (size_t)ctx->max_lds) return fail(RHMC_ERR_UNSUPPORTED, "mh_pk LDS");
+  k.Df = ctx->d_Df;
+  const int64_t waves = (k.n + MP::PK::CPW - 1) / MP::PK::CPW;
+  const dim3 grid((unsigned)((waves + W - 1) / W)), block(W * kWave);
+  hipLaunchKernelGGL((mh_pk_v0<IMG, 10>), grid, block, lds, s, k, V);
+  HIP_TRY(hipGetLastError());
+  for (int it = 0; it < k.n_iter; ++it) {
+    if (sched_active(sc)) {
+      const rhmc_params Pl = sched_params(*P, sc, it);
+      int rc = make_consts(&Pl, &k.c);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL((mh_pk_iter<IMG, 10>), grid, block, lds, s, k, it, V);
+    HIP_TRY(hipGetLastError());
+  }
+  return RHMC_OK;
+}
+
+// The MH outer loop on device buffers (sampler_RHMC.py:1018-1083): per
+// iteration begin -> n_steps fused leapfrog -> V(q') -> accept, all queued on
+// `s` with no host synchronisation.  `rec` holds device pointers (nullable);
+// `sc` (nullable, host arrays) schedules g_ff2 / beta per iteration
+// (sampler_RHMC.py:1010-1016, sched_params).
+int run_mh(rhmc_ctx* ctx, const rhmc_params* P, double* d_q, int64_t n, int32_t K,
+           int32_t n_iter, int32_t n_steps, int32_t f_pos, const double* d_z, const double* d_u,
+           uint64_t seed, const rhmc_mh_record* rec, hipStream_t s,
+           const rhmc_mh_schedule* sc = nullptr) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  if (n_iter < 0 || n_steps < 0) return fail(RHMC_ERR_ARG, "n_iter/n_steps < 0");
+  if (sc && (sc->n_g_ff2 < 0 || sc->n_beta < 0 || (sc->n_g_ff2 > 0 && !sc->g_ff2) ||
+             (sc->n_beta > 0 && !sc->beta)))
+    return fail(RHMC_ERR_ARG, "schedule: negative size or NULL array with a nonzero size");
+  const bool sched = sched_active(sc);
+  if (sched)  // every iteration's parameters must be valid, not only the first's
+    for (int it = 0; it < n_iter; ++it) {
+      const rhmc_params Pl = sched_params(*P, sc, it);
+      Consts cl;
+      if ((rc = make_consts(&Pl, &cl))) return rc;
+    }
+  if (n == 0 || n_iter == 0) return RHMC_OK;
+  f_pos = f_pos != 0 ? RHMC_V_FLUX_WALL : 0;
+  Plan fused;
+  if ((rc = plan_for(ctx, c, Op::MhFused, K, n, &fused))) return rc;
+  if (fused.family == Family::RegWin1) {
+    MhK1Args k;
+    k.q = d_q;
+    k.D = ctx->d_D;
+    k.Df = nullptr;
+    k.z = d_z;
+    k.u = d_u;
+    set_record(k, rec);
+    k.n = n;
+    k.n_iter = n_iter;
+    k.n_steps = n_steps;
+    k.f_pos = f_pos;
+    k.it0 = 0;
+    k.seed = seed;
+    k.c = c;
+    if (!sched) return launch_mh_k1(ctx, fused, k, s);
+    // scheduled: one launch per iteration with its own constants (V(q) is
+    // re-evaluated at each launch's start: the same operations, the same value)
+    for (int it = 0; it < n_iter; ++it) {
+      const rhmc_params Pl = sched_params(*P, sc, it);
+      if ((rc = make_consts(&Pl, &k.c))) return rc;
+      k.n_iter = 1;
+      k.it0 = it;
+      if ((rc = launch_mh_k1(ctx, fused, k, s))) return rc;
+    }
+    return RHMC_OK;
+  }
+  if (fused.family == Family::PixMajor) {
+    MhKArgs k;
+    k.q = d_q;
+    k.Df = nullptr;
+    k.z = d_z;
+    k.u = d_u;
+    set_record(k, rec);
+    k.n = n;
+    k.K = K;
+    k.n_iter = n_iter;
+    k.n_steps = n_steps;
+    k.f_pos = f_pos;
+    k.seed = seed;
+    k.c = c;
+    if ((rc = ensure_mh_scratch(ctx, (size_t)n * sizeof(double) + 256))) return rc;
+    double* V = (double*)ctx->mh_scratch;
+    return with_side2(ctx->rows, [&](auto img) {
+      return launch_mh_pk<decltype(img)::value>(ctx, k, V, s, P, sc);
+    });
+  }
+  const size_t sb = (size_t)n * 3 * K * sizeof(double), eb = (size_t)n * sizeof(double);
+  if ((rc = ensure_mh_scratch(ctx, 2 * sb + 3 * eb + 256))) return rc;
+  char* b = (char*)ctx->mh_scratch;
+  MhArgs m;
+  m.q = d_q;
+  m.q_prop = (double*)b;
+  m.p = (double*)(b + sb);
+  m.V_cur = (double*)(b + 2 * sb);
+  m.V_prop = (double*)(b + 2 * sb + eb);
+  m.E0 = (double*)(b + 2 * sb + 2 * eb);
+  m.z = d_z;
+  m.u = d_u;
+  set_record(m, rec);
+  m.n = n;
+  m.K = K;
+  m.seed = seed;
+  m.c = c;
+  if ((rc = launch_energy(ctx, c, d_q, nullptr, m.V_cur, nullptr, n, K, f_pos, s))) return rc;
+  // V reads beta through the repulsion term: a beta schedule re-evaluates
+  // V(q) at each iteration's start, like the reference's V_initial (:1025)
+  const bool v_sched = sched && c.use_Vc && sc->beta && sc->n_beta > 0;
+  // begin / end: one thread per chain for few stars, one wave per chain
+  // (lanes over the coordinates) from 8 stars
+  const bool wave_mh = K >= 8;
+  const dim3 grid((unsigned)(wave_mh ? (n + 3) / 4 : (n + 255) / 256)), block(256);
+  for (int it = 0; it < n_iter; ++it) {
+    m.iter = it;
+    const rhmc_params Pl = sched ? sched_params(*P, sc, it) : *P;
+    if (sched) {
+      if ((rc = make_consts(&Pl, &m.c))) return rc;
+      if (v_sched &&
+          (rc = launch_energy(ctx, m.c, d_q, nullptr, m.V_cur, nullptr, n, K, f_pos, s)))
+        return rc;
+    }
+    if (wave_mh)
+      hipLaunchKernelGGL(mh_begin_wave_kernel, grid, block, 0, s, m);
+    else
+      hipLaunchKernelGGL(mh_begin_kernel, grid, block, 0, s, m);
+    HIP_TRY(hipGetLastError());
+    if ((rc = launch_leapfrog(ctx, &Pl, m.q_prop, m.p, n, K, n_steps, nullptr, nullptr, s)))
+      return rc;
+    if ((rc = launch_energy(ctx, m.c, m.q_prop, nullptr, m.V_prop, nullptr, n, K, f_pos, s)))
+      return rc;
+    if (wave_mh)
+      hipLaunchKernelGGL(mh_end_wave_kernel, grid, block, 0, s, m);
+    else
+      hipLaunchKernelGGL(mh_end_kernel, grid, block, 0, s, m);
+    HIP_TRY(hipGetLastError());
+  }
+  return RHMC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Explicit integrators and HMC_random
+// ---------------------------------------------------------------------------
+
+int launch_integrate(rhmc_ctx* ctx, const rhmc_params* P, int32_t solver, double* d_q,
+                     double* d_p, int64_t n, int32_t K, int32_t n_steps, int32_t f_pos,
+                     int32_t* d_st, hipStream_t s) {
+  if (solver == RHMC_SOLVER_IMPLICIT)
+    return launch_leapfrog(ctx, P, d_q, d_p, n, K, n_steps, nullptr, d_st, s);
+  if (solver < RHMC_SOLVER_HMC || solver > RHMC_SOLVER_RHMC_LEAPFROG)
+    return fail(RHMC_ERR_ARG, "unknown solver");
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  if (n_steps < 0) return fail(RHMC_ERR_ARG, "n_steps < 0");
+  if (n == 0) return RHMC_OK;
+  Plan pl;
+  if ((rc = plan_for(ctx, c, Op::Integrate, K, n, &pl))) return rc;
+  const int fp = f_pos != 0;
+  switch (pl.family) {
+    case Family::RegWin1: {  // rhmc_tiledr.hpp
+      LeapArgsK1 t = k1_args(ctx, c, d_q, d_p, nullptr, d_st, n, n_steps);
+      if (pl.f32) t.Df = ctx->d_Df;
+      HIP_TRY(hipSetDevice(ctx->device));
+      return with_solver(solver, [&](auto sv) {
+        return launch_k1_w28(ctx, pl.f32, n,
+                             [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
+          using DT = typename decltype(dt)::type;
+          hipLaunchKernelGGL(
+              (integrate_k1_tiledr<decltype(img)::value, 28, DT, decltype(sv)::value>), grid,
+              block, lds, s, t, fp);
+        });
+      });
+    }
+    case Family::PixMajor:
+    case Family::MultiWin: {
+      const LeapArgsKR t = kr_args(ctx, c, d_q, d_p, nullptr, d_st, n, K, n_steps);
+      HIP_TRY(hipSetDevice(ctx->device));
+      return with_solver(solver, [&](auto sv) {
+        return launch_multi<decltype(sv)::value>(ctx, pl, t, fp, s);
+      });
+    }
+    default: {  // slotted (integrate_win_kernel)
+      LeapArgs a = leap_args(ctx, c, d_q, d_p, nullptr, d_st, n, K, n_steps);
+      SlotShape sh;
+      if ((rc = slotted_shape(ctx, pl, K, n, s, true, &a.g, &sh))) return rc;
+      return with_solver(solver, [&](auto sv) {
+        return with_path(pl.path, K, [&](auto gt, auto st) {
+          using G = typename decltype(gt)::type;
+          hipLaunchKernelGGL((integrate_win_kernel<G, decltype(sv)::value, decltype(st)::value>),
+                             sh.grid, sh.block, sh.lds, s, a, fp);
+          return launch_status();
+        });
+      });
+    }
+  }
+}
+
+int launch_hmc_random(rhmc_ctx* ctx, const rhmc_params* P, const double* d_dt, double* d_q,
+                      double* d_p, const int32_t* d_steps, int64_t n, int32_t K, int32_t* d_st,
+                      hipStream_t s) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  if (n == 0) return RHMC_OK;
+  if (!d_dt || !d_steps) return fail(RHMC_ERR_ARG, "dt/steps is NULL");
+  Plan pl;
+  if ((rc = plan_for(ctx, c, Op::HmcRandom, K, n, &pl))) return rc;
+  switch (pl.family) {
+    case Family::RegWin1: {
+      LeapArgsK1 t = k1_args(ctx, c, d_q, d_p, nullptr, d_st, n, 0);
+      if (pl.f32) t.Df = ctx->d_Df;
+      HIP_TRY(hipSetDevice(ctx->device));
+      return launch_k1_w28(ctx, pl.f32, n,
+                           [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
+        using DT = typename decltype(dt)::type;
+        hipLaunchKernelGGL((hmc_random_k1_tiledr<decltype(img)::value, DT>), grid, block, lds, s,
+                           t, d_dt, d_steps);
+      });
+    }
+    case Family::PixMajor:
+    case Family::MultiWin: {
+      const LeapArgsKR t = kr_args(ctx, c, d_q, d_p, nullptr, d_st, n, K, 0, d_dt, d_steps);
+      HIP_TRY(hipSetDevice(ctx->device));
+      return launch_multi<kSolverHmcRandom>(ctx, pl, t, 0, s);
+    }
+    default: {  // slotted (hmc_random_win_kernel)
+      LeapArgs a = leap_args(ctx, c, d_q, d_p, nullptr, d_st, n, K, 0);
+      SlotShape sh;
+      if ((rc = slotted_shape(ctx, pl, K, n, s, true, &a.g, &sh))) return rc;
+      return with_path(pl.path, K, [&](auto gt, auto st) {
+        using G = typename decltype(gt)::type;
+        hipLaunchKernelGGL((hmc_random_win_kernel<G, decltype(st)::value>), sh.grid, sh.block,
+                           sh.lds, s, a, d_dt, d_steps);
+        return launch_status();
+      });
+    }
+  }
+}
+
+// Model image / Poisson realisations (rhmc_datagen.hpp) into d_out
+// [max(n_real,1)][rows][cols].
+int launch_gen_image(rhmc_ctx* ctx, const rhmc_params* P, const double* d_q, int32_t K,
+                     int32_t rows, int32_t cols, int32_t n_real, uint64_t seed, double* d_out,
+                     hipStream_t s) {
+  DataArgs a;
+  int rc = make_consts(P, &a.c);
+  if (rc) return rc;
+  if (K < 0 || K > (1 << 20)) return fail(RHMC_ERR_ARG, "K must be in [0, 2^20]");
+  if (rows < 1 || cols < 1) return fail(RHMC_ERR_ARG, "rows/cols must be >= 1");
+  if (n_real < 0) return fail(RHMC_ERR_ARG, "n_real < 0");
+  if (K > 0 && !d_q) return fail(RHMC_ERR_ARG, "q is NULL");
+  if (!d_out) return fail(RHMC_ERR_ARG, "out is NULL");
+  const int64_t npix = (int64_t)rows * cols;
+  const int64_t total = npix * (n_real > 0 ? n_real : 1);
+  if (total > ((int64_t)1 << 36)) return fail(RHMC_ERR_ARG, "rows*cols*n_real too large");
+  a.q = d_q;
+  a.out = d_out;
+  a.K = K;
+  a.rows = rows;
+  a.cols = cols;
+  a.poisson = n_real > 0;
+  a.n_real = n_real;
+  a.seed = seed;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  hipLaunchKernelGGL(datagen_kernel, grid, block, 0, s, a);
+  return launch_status();
+}
+
+}  // namespace

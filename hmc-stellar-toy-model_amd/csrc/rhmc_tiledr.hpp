@@ -35,16 +35,11 @@
 #pragma once
 #include "rhmc_exp.hpp"
 #include "rhmc_k1step.hpp"
+#include "rhmc_select.hpp"  // reg_window_ok: when a window is exact
 #include "rhmc_wave.hpp"
 #include "rhmc_windowed.hpp"
 
 namespace rhmc {
-
-// exp(-(WIN/2)^2 / (2 sigma^2)) <= 2^-62 (62 ln 2 = 42.975)?
-__host__ __device__ inline bool reg_window_ok(int win, double inv_two_sig2) {
-  const double h = 0.5 * win;
-  return h * h * inv_two_sig2 >= 42.98;
-}
 
 template <int PAT>
 __device__ __forceinline__ double swizzle_d(double v) {

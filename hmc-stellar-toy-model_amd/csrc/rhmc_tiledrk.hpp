@@ -68,7 +68,7 @@ struct KRStar {  // LDS star table entry
 };
 
 // TAB variant: Lambda over all stars in an unrolled loop (A/B knob), for at
-// most TABK stars (kr_tables in rhmc_kernels.hip: K <= 16).
+// most TABK stars (kr_tables in rhmc_select.hpp: K <= 16).
 #ifndef RHMC_KR_ALLSTARS
 #define RHMC_KR_ALLSTARS 1
 #endif

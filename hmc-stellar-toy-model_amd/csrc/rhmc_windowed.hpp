@@ -467,7 +467,7 @@ __device__ double win_potential(const double* __restrict__ D, double* ey,
   return wave_sum_dpp(v);
 }
 
-// Gradient policy of the slotted kernels (rhmc_kernels.hip) on windowed
+// Gradient policy of the slotted kernels (rhmc_perwave.hpp) on windowed
 // tables: any square image, D read from global memory (L2).
 struct WinG {
   static __host__ __device__ size_t lds_bytes(int waves, int K) {

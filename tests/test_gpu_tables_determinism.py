@@ -1,5 +1,5 @@
 """Run-to-run determinism of the windowed paths whose factor tables live in
-global memory (rhmc_windowed.hpp WinGG, from 65 stars; rhmc_kernels.hip
+global memory (rhmc_windowed.hpp WinGG, from 65 stars; rhmc_launch.hpp
 work_tables).  The MH loop of run_RHMC (sampler_RHMC.py:697-760) over the
 implicit leapfrog (:522-566) is a deterministic function of its start and seed,
 so repeated launches -- on one stream, on two streams, after the table buffer

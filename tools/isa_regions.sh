@@ -1,20 +1,30 @@
 #!/bin/bash
-# Instruction counts per step-loop region of a kernel (tools only): builds
-# librhmc with -DRHMC_MARKS (s_setprio markers in rhmc_k1step.hpp) into
-# /tmp/isa and splits the disassembly at the markers.  usage: isa_regions.sh NAME_SUBSTRING
-cd /root/repo/hmc-stellar-toy-model_amd
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I../include -Icsrc -DRHMC_MARKS ${EXTRA:-} -c -o /tmp/isa/mark.o csrc/rhmc_kernels.hip 2>&1 | grep error
-mkdir -p /tmp/isa; cd /tmp/isa
-/opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --input=mark.o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=km.co 2>/dev/null || { /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o libmark.so mark.o; /opt/rocm/lib/llvm/bin/llvm-objcopy --dump-section=.hip_fatbin=fatm.bin libmark.so; /opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --input=fatm.bin --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=km.co; }
-/opt/rocm/lib/llvm/bin/llvm-objdump -d --mcpu=gfx950 km.co > km.s
+# Instruction counts per step-loop region of a kernel (tools only): builds the
+# library variant `marks` with -DRHMC_MARKS (s_setprio markers in
+# rhmc_k1step.hpp; `make variant`, both translation units) and splits the
+# disassembly at the markers.  usage: [EXTRA=-D...] isa_regions.sh NAME_SUBSTRING
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+make -s -C "$ROOT/hmc-stellar-toy-model_amd" variant NAME=marks FLAGS="-DRHMC_MARKS ${EXTRA:-}" || exit 1
+mkdir -p /tmp/isa; cd /tmp/isa || exit 1
+/opt/rocm/lib/llvm/bin/llvm-objcopy --dump-section=.hip_fatbin=fatm.bin "$ROOT/build/variants/lib_marks.so"
 python3 - "$1" <<'PY'
-import re,sys
+import re,subprocess,sys
 from collections import Counter
+LLVM='/opt/rocm/lib/llvm/bin/'
+# one offload bundle per translation unit, concatenated by the linker
+data=open('fatm.bin','rb').read()
+starts=[m.start() for m in re.finditer(rb'__CLANG_OFFLOAD_BUNDLE__',data)]
 funcs={};cur=None
-for line in open('km.s'):
-    m=re.match(r"^[0-9a-f]+ <(\S+)>:",line)
-    if m: cur=m.group(1); funcs[cur]=[]; continue
-    if cur and line.strip(): funcs[cur].append(line.split('//')[0].strip())
+for i,st in enumerate(starts):
+    open('b%d.bin'%i,'wb').write(data[st:starts[i+1] if i+1<len(starts) else len(data)])
+    subprocess.run([LLVM+'clang-offload-bundler','--unbundle','--type=o','--input=b%d.bin'%i,
+                    '--targets=hipv4-amdgcn-amd-amdhsa--gfx950','--output=km%d.co'%i],check=True)
+    out=subprocess.run([LLVM+'llvm-objdump','-d','--mcpu=gfx950','km%d.co'%i],check=True,
+                       capture_output=True,text=True).stdout
+    for line in out.splitlines():
+        m=re.match(r"^[0-9a-f]+ <(\S+)>:",line)
+        if m: cur=m.group(1); funcs[cur]=[]; continue
+        if cur and line.strip(): funcs[cur].append(line.split('//')[0].strip())
 k=[k for k in funcs if sys.argv[1] in k][0]
 v=funcs[k]
 open('m.s','w').write('\n'.join(v))

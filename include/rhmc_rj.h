@@ -34,9 +34,9 @@
  * its own, held (a mutex) for the whole run, so concurrent rhmc_rj_run calls
  * on one device serialise pipe by pipe; the caller's current device is
  * restored on return.  The pipes' host work runs on one process-wide thread
- * pool per size (n_threads - pipes workers, kept for the process's lifetime,
- * shared by concurrent runs); the pipe threads take its chunks while their
- * streams run.  Host <-> device data moves through coherent pinned host
+ * pool per size (n_threads - pipes workers, kept between runs until
+ * rhmc_rj_release drops the pools no run is using, shared by concurrent
+ * runs); the pipe threads take its chunks while their streams run.  Host <-> device data moves through coherent pinned host
  * memory mapped into the device (the engine's kernels read and write it at
  * its device address): no copy-engine transfers.
  *
@@ -185,8 +185,10 @@ int rhmc_rj_run_physics(const rhmc_rj_physics* phys, const rhmc_params* P,
                         int64_t n, const rhmc_rj_record* rec);
 
 /* Free the buffers, streams and events rhmc_rj_run keeps between runs (see
- * Retention above) on `device`, or on every device when device < 0.  A later
- * run allocates them again.  Not to be called from inside a physics callback. */
+ * Retention above) on `device`, or on every device when device < 0, and the
+ * idle host thread pools.  A later run allocates them again.  May be called
+ * while a run is in progress on another thread: it waits for that run, pipe
+ * by pipe.  Not to be called from inside a physics callback. */
 int rhmc_rj_release(int32_t device);
 
 /* The NumPy legacy stream replica, for parity checks: n draws from

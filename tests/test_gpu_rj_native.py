@@ -343,6 +343,41 @@ def test_native_checkpoint_resume_on_the_engine(gpu_lib):
     assert (a.move_chain[a.A_chain] > 0).any()
 
 
+def test_native_release_then_run_again(gpu_lib):
+    """rj_native.release() frees both pipes' buffers, streams and chain state
+    (rhmc_rj_release); the next run sets them up again and every record and
+    final state equals the first run's bit for bit.  32x32, 2-4 stars, so the
+    phases are ragged pixel-major launches, and chain 6's death from two stars
+    in iteration 0 takes the packed one-star launch.  Releasing with nothing
+    held is not an error."""
+    from rhmc_amd import rj_native
+    z = load_golden("rj")
+    name = "rj_all"
+    par = R.params_from_npz(z, name + "/par_")
+    starts = [m[:2 + c % 3] for c, m in
+              enumerate(_starts(z[name + "/q_model"], 24, np.random.RandomState(7)))]
+    kw = dict(f_pos=True, delta=1e-6, Niter=6, Nsteps=5, dt=0.05, N_max=8,
+              P_move=[0.4, 0.3, 0.3], n_pipes=2)
+    keys = ("q_chain", "p_chain", "E_chain", "V_chain", "T_chain", "A_chain", "move_chain",
+            "N_chain", "flag_chain", "rj_rng_states")
+
+    def run():
+        g = _gym(par)
+        g.D = z[name + "/D"]
+        q = g.run_RHMC_rj_batched([m.copy() for m in starts], list(range(1200, 1224)), **kw)
+        return [np.array(x) for x in q], {k: np.array(getattr(g, k)) for k in keys}
+    qa, ra = run()
+    rj_native.release()
+    qb, rb = run()
+    for k in keys:
+        assert ra[k].tobytes() == rb[k].tobytes(), k
+    assert len(qa) == len(qb) and all(np.array_equal(x, y) for x, y in zip(qa, qb))
+    assert ((ra["move_chain"][0] == 2) & (ra["N_chain"][0] == 2)).any()
+    assert (ra["move_chain"] > 0).any() and ra["A_chain"].any()
+    rj_native.release(0)
+    rj_native.release(-1)
+
+
 @pytest.mark.parametrize("golden,name", [("rj", "rj_bd"), ("rj", "rj_sm"), ("rj", "rj_all"),
                                          ("mh", "mh1"), ("mh", "mh3"), ("mh_sched", "g1"),
                                          ("mh_sched", "g3"), ("mh_sched", "g3vc")])

@@ -26,6 +26,7 @@
 #include "rhmc_tiledrk.hpp"
 #include "rhmc_mhk1.hpp"
 #include "rhmc_mhpk.hpp"
+#include "rhmc_peaks.hpp"
 #include "rhmc_pixk.hpp"
 #include "rhmc_wave.hpp"
 #include "rhmc_windowed.hpp"
@@ -75,6 +76,8 @@ struct rhmc_ctx {
   int kernel = RHMC_KERNEL_AUTO;   // RHMC_OPT_KERNEL
   int mh_fused = 1;                // RHMC_OPT_MH_FUSED
   int window_split = 0;            // RHMC_OPT_WINDOW_SPLIT (0: by batch size)
+  int peaks_fused = 1;             // RHMC_OPT_PEAKS_FUSED
+  int32_t* h_pin = nullptr;        // pinned word: find_peaks' stepwise path polls through it
   int table_mode = RHMC_TABLES_STREAM;  // RHMC_OPT_TABLES (diagnostic modes, rhmc.h)
   // WinGG factor tables, one buffer per stream (work_tables).  A launch holds a
   // lease (shared_ptr) on its buffer from the lookup until the launch is
@@ -116,6 +119,26 @@ int check_common(rhmc_ctx* ctx, int64_t n_chains, int32_t K) {
   if (n_chains < 0) return fail(RHMC_ERR_ARG, "n_chains < 0");
   if (K < 1 || K > kMaxK) return fail(RHMC_ERR_ARG, "K must be in [1, 1024]");
   if (n_chains > ((int64_t)1 << 40)) return fail(RHMC_ERR_ARG, "n_chains too large");
+  return RHMC_OK;
+}
+
+// The checks the two find_peaks entry points share (n == 0 after them: a
+// no-op); the arguments first, so that they are checked without a device too.
+int check_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* o, const double* q,
+                int64_t n) {
+  if (!P) return fail(RHMC_ERR_ARG, "params is NULL");
+  if (!o) return fail(RHMC_ERR_ARG, "opts is NULL");
+  if (n < 0) return fail(RHMC_ERR_ARG, "n < 0");
+  if (n > ((int64_t)1 << 31)) return fail(RHMC_ERR_ARG, "n too large (2^31 seeds at most)");
+  if (o->reserved != 0) return fail(RHMC_ERR_ARG, "opts.reserved must be 0");
+  if (o->n_step < 0 || o->n_step > 1000000)
+    return fail(RHMC_ERR_ARG, "opts.n_step must be in [0, 10^6]");
+  if (!(std::isfinite(o->f_lim) && std::isfinite(o->dt_f_coeff) &&
+        std::isfinite(o->dt_xy_coeff) && std::isfinite(o->rel_tol)))
+    return fail(RHMC_ERR_ARG, "opts: non-finite coefficient");
+  if (!q) return fail(RHMC_ERR_ARG, "q is NULL");
+  if (!ctx) return fail(RHMC_ERR_ARG, "ctx is NULL");
+  if (n > 0 && !ctx->d_D) return fail(RHMC_ERR_ARG, "no image uploaded");
   return RHMC_OK;
 }
 
@@ -283,6 +306,11 @@ int rhmc_ctx_set_option(rhmc_ctx* ctx, int32_t option, int32_t value) {
       if (value != 0 && value != 1) return fail(RHMC_ERR_ARG, "RHMC_OPT_MH_FUSED must be 0 or 1");
       ctx->mh_fused = value;
       return RHMC_OK;
+    case RHMC_OPT_PEAKS_FUSED:
+      if (value != 0 && value != 1)
+        return fail(RHMC_ERR_ARG, "RHMC_OPT_PEAKS_FUSED must be 0 or 1");
+      ctx->peaks_fused = value;
+      return RHMC_OK;
     case RHMC_OPT_WINDOW_SPLIT:
       if (value != 0 && value != 1 && value != 2 && value != 4)
         return fail(RHMC_ERR_ARG, "RHMC_OPT_WINDOW_SPLIT must be 0, 1, 2 or 4");
@@ -313,6 +341,7 @@ int rhmc_ctx_get_option(rhmc_ctx* ctx, int32_t option, int32_t* value) {
     case RHMC_OPT_MH_FUSED: *value = ctx->mh_fused; return RHMC_OK;
     case RHMC_OPT_WINDOW_SPLIT: *value = ctx->window_split; return RHMC_OK;
     case RHMC_OPT_TABLES: *value = ctx->table_mode; return RHMC_OK;
+    case RHMC_OPT_PEAKS_FUSED: *value = ctx->peaks_fused; return RHMC_OK;
     default: return fail(RHMC_ERR_ARG, "unknown option " + std::to_string(option));
   }
 }
@@ -332,6 +361,7 @@ void rhmc_ctx_destroy(rhmc_ctx* ctx) {
   if (ctx->d_flag) (void)hipFree(ctx->d_flag);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->mh_scratch) (void)hipFree(ctx->mh_scratch);
+  if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (!ctx->tabs.empty() || !ctx->kept.empty())
     (void)hipDeviceSynchronize();   // tables may serve user streams
   for (auto& t : ctx->tabs)
@@ -638,6 +668,31 @@ int rhmc_hmc_random(rhmc_ctx* ctx, const rhmc_params* P, const double* dt, doubl
   return st.run([&] {
     return launch_hmc_random(ctx, P, st.dev<double>(id), st.dev<double>(iq), st.dev<double>(ip),
                              st.dev<int32_t>(in), n_chains, K, st.dev<int32_t>(is), ctx->stream);
+  });
+}
+
+int rhmc_find_peaks_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* opts,
+                           double* d_q, int64_t n, int32_t* d_steps, int32_t* d_status,
+                           double* d_V, void* stream) {
+  if (int rc = check_peaks(ctx, P, opts, d_q, n)) return rc;
+  if (n == 0) return RHMC_OK;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  return launch_find_peaks(ctx, P, opts, d_q, n, d_steps, d_status, d_V, s);
+}
+
+int rhmc_find_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* opts, double* q,
+                    int64_t n, int32_t* steps, int32_t* status, double* V) {
+  if (int rc = check_peaks(ctx, P, opts, q, n)) return rc;
+  if (n == 0) return RHMC_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  Staging st(ctx);  // an output not asked for has no part (NULL to the kernels)
+  const int iq = st.add(q, (size_t)n * 3 * sizeof(double), Staging::kInOut);
+  const int is = st.add(steps, steps ? (size_t)n * sizeof(int32_t) : 0, Staging::kOut);
+  const int it = st.add(status, status ? (size_t)n * sizeof(int32_t) : 0, Staging::kOut);
+  const int iV = st.add(V, V ? (size_t)n * sizeof(double) : 0, Staging::kOut);
+  return st.run([&] {
+    return launch_find_peaks(ctx, P, opts, st.dev<double>(iq), n, st.dev<int32_t>(is),
+                             st.dev<int32_t>(it), st.dev<double>(iV), ctx->stream);
   });
 }
 

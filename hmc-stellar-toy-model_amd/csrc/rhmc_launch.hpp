@@ -9,8 +9,8 @@
 namespace {
 
 SelectIn select_in(const rhmc_ctx* ctx) {
-  return SelectIn{ctx->rows,  ctx->cols,   ctx->img_f32,  ctx->max_lds,
-                  ctx->n_cu,  ctx->kernel, ctx->mh_fused, ctx->window_split};
+  return SelectIn{ctx->rows,  ctx->cols,   ctx->img_f32,  ctx->max_lds,     ctx->n_cu,
+                  ctx->kernel, ctx->mh_fused, ctx->window_split, ctx->peaks_fused};
 }
 
 // The plan of one call; an unsupported configuration is the error here.
@@ -1045,6 +1045,99 @@ int launch_hmc_random(rhmc_ctx* ctx, const rhmc_params* P, const double* d_dt, d
       });
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// find_peaks' seed descent (rhmc_peaks.hpp)
+// ---------------------------------------------------------------------------
+
+int ensure_pin(rhmc_ctx* ctx) {
+  if (ctx->h_pin) return RHMC_OK;
+  if (hipHostMalloc((void**)&ctx->h_pin, 64, hipHostMallocDefault) != hipSuccess) {
+    ctx->h_pin = nullptr;
+    return fail(RHMC_ERR_NOMEM, "hipHostMalloc of the pinned word failed");
+  }
+  return RHMC_OK;
+}
+
+// The stepwise path: per step gradient -> update -> energy -> test, with the
+// library's K = 1 launches; every 16 steps the count of seeds still
+// descending comes back through pinned memory and ends the loop at 0.
+int run_peaks_stepwise(rhmc_ctx* ctx, const Consts& c, const rhmc_peaks_opts& o, double* d_q,
+                       int64_t n, int32_t* d_steps, int32_t* d_status, double* d_V,
+                       hipStream_t s) {
+  int rc;
+  Plan gp;
+  if ((rc = plan_for(ctx, c, Op::Gradient, 1, n, &gp))) return rc;
+  const size_t qb = ((size_t)n * 3 * sizeof(double) + 255) & ~(size_t)255;
+  const size_t eb = ((size_t)n * sizeof(double) + 255) & ~(size_t)255;
+  if ((rc = ensure_mh_scratch(ctx, 2 * qb + 5 * eb + 256))) return rc;
+  if ((rc = ensure_pin(ctx))) return rc;
+  char* b = (char*)ctx->mh_scratch;
+  PeaksStepArgs a;
+  a.q = d_q;
+  double* grad = (double*)b;
+  a.grad = grad;
+  a.q_new = (double*)(b + qb);
+  double* V_new = (double*)(b + 2 * qb);
+  a.V_new = V_new;
+  a.V_prev = (double*)(b + 2 * qb + eb);
+  a.V_last = (double*)(b + 2 * qb + 2 * eb);
+  a.steps = (int32_t*)(b + 2 * qb + 3 * eb);
+  a.status = (int32_t*)(b + 2 * qb + 4 * eb);
+  a.n_active = (int32_t*)(b + 2 * qb + 5 * eb);
+  a.n = n;
+  a.f_lim = o.f_lim;
+  a.dt_f_coeff = o.dt_f_coeff;
+  a.dt_xy_coeff = o.dt_xy_coeff;
+  a.rel_tol = o.rel_tol;
+  a.n_step = o.n_step;
+  a.step = 0;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  const int f_pos = RHMC_V_NO_POSCHECK;            // V_single has no support check
+  if ((rc = launch_energy(ctx, c, d_q, nullptr, a.V_prev, nullptr, n, 1, f_pos, s))) return rc;
+  hipLaunchKernelGGL(peaks_begin_kernel, grid, block, 0, s, a);
+  HIP_TRY(hipGetLastError());
+  for (int i = 0; i < o.n_step; ++i) {
+    a.step = i;
+    const bool poll = i % 16 == 15;
+    if ((rc = launch_gradient(ctx, gp, c, d_q, grad, n, 1, 0, s))) return rc;
+    hipLaunchKernelGGL(peaks_update_kernel<0>, grid, block, 0, s, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc = launch_energy(ctx, c, a.q_new, nullptr, V_new, nullptr, n, 1, f_pos, s))) return rc;
+    if (poll) HIP_TRY(hipMemsetAsync(a.n_active, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(peaks_update_kernel<1>, grid, block, 0, s, a);
+    HIP_TRY(hipGetLastError());
+    if (poll) {
+      HIP_TRY(hipMemcpyAsync(ctx->h_pin, a.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      if (*ctx->h_pin == 0) break;
+    }
+  }
+  hipLaunchKernelGGL(peaks_end_kernel, grid, block, 0, s, a, d_steps, d_status, d_V);
+  return launch_status();
+}
+
+int launch_find_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* o, double* d_q,
+                      int64_t n, int32_t* d_steps, int32_t* d_status, double* d_V,
+                      hipStream_t s) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  c.use_prior = 0;                                 // V_single / dVdq_single have neither
+  c.use_Vc = 0;
+  c.f_lim = o->f_lim;
+  HIP_TRY(hipSetDevice(ctx->device));
+  Plan pl;
+  if ((rc = plan_for(ctx, c, Op::Peaks, 1, n, &pl))) return rc;
+  if (pl.family != Family::RegWin1)
+    return run_peaks_stepwise(ctx, c, *o, d_q, n, d_steps, d_status, d_V, s);
+  const PeaksArgs k{d_q, d_steps, d_status, d_V, ctx->d_D, pl.f32 ? ctx->d_Df : nullptr, n,
+                    o->f_lim, o->dt_f_coeff, o->dt_xy_coeff, o->rel_tol, o->n_step, /*pad*/ 0, c};
+  return launch_k1_w28(ctx, pl.f32, n, [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
+    using DT = typename decltype(dt)::type;
+    hipLaunchKernelGGL((peaks_k1_tiledr<decltype(img)::value, DT>), grid, block, lds, s, k);
+  });
 }
 
 // Model image / Poisson realisations (rhmc_datagen.hpp) into d_out

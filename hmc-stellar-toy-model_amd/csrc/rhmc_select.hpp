@@ -79,9 +79,10 @@ struct SelectIn {
   int kernel = RHMC_KERNEL_AUTO;   // RHMC_OPT_KERNEL
   int mh_fused = 1;                // RHMC_OPT_MH_FUSED
   int window_split = 0;            // RHMC_OPT_WINDOW_SPLIT (0: by batch size)
+  int peaks_fused = 1;             // RHMC_OPT_PEAKS_FUSED
 };
 
-enum class Op { Step, Integrate, HmcRandom, Energy, Gradient, MhFused };
+enum class Op { Step, Integrate, HmcRandom, Energy, Gradient, MhFused, Peaks };
 
 enum class Family {
   RegWin1,      // one-star register-window (rhmc_tiledr.hpp, rhmc_mhk1.hpp)
@@ -90,7 +91,8 @@ enum class Family {
   MultiWin,     // multi-star register-window (rhmc_tiledrk.hpp)
   Slotted,      // one wave per chain, a gradient policy (*_win_kernel)
   LdsImage,     // one wave per chain, image in LDS (K <= 16)
-  None,         // MhFused only: no fused kernel, the four-kernel loop runs
+  None,         // MhFused: no fused kernel, the four-kernel loop runs;
+                // Peaks: the stepwise path (gradient / update / energy launches)
   Unsupported   // message holds the error text (RHMC_ERR_UNSUPPORTED)
 };
 
@@ -234,6 +236,8 @@ constexpr OpRules op_rules(Op op) {
     case Op::Gradient: return {false, false, false, false, false, true, Policy::WinG};
     // Fused MH: see select_mh_fused.
     case Op::MhFused: break;
+    // The seed descent of find_peaks: see select_peaks.
+    case Op::Peaks: break;
   }
   return {false, false, false, false, false, false, Policy::WinG};
 }
@@ -264,10 +268,31 @@ inline Plan select_mh_fused(const SelectIn& s, bool use_Vc, double inv_two_sig2,
   return pl;
 }
 
+// find_peaks' seed descent (rhmc_peaks.hpp), always one star per seed: the
+// one-launch kernel on sides 32/48/64 under the 28-px test like the
+// integrators (only those instantiations exist) and, like them, at every
+// batch size (there is no lane-group descent).  RHMC_OPT_PEAKS_FUSED = 0, a
+// forced per-wave family (GENERIC / WINDOWED) or any other configuration
+// takes the stepwise path (Family::None): the K = 1 gradient and energy
+// launches of this header's Gradient / Energy rows around peaks_update_kernel.
+inline Plan select_peaks(const SelectIn& s, double inv_two_sig2) {
+  Plan pl;
+  pl.family = Family::None;
+  if (!s.peaks_fused || per_wave_forced(s)) return pl;
+  const int side = s.rows;
+  if (s.rows == s.cols && (side == 32 || side == 48 || side == 64) &&
+      reg_window_ok(28, inv_two_sig2)) {
+    pl.family = Family::RegWin1;
+    pl.f32 = s.img_f32;
+  }
+  return pl;
+}
+
 // The kernel family and its compile-time choices for one call.
 inline Plan select(const SelectIn& s, bool use_Vc, double inv_two_sig2, Op op, int K,
                    int64_t n_chains) {
   if (op == Op::MhFused) return select_mh_fused(s, use_Vc, inv_two_sig2, K, n_chains);
+  if (op == Op::Peaks) return select_peaks(s, inv_two_sig2);
   const OpRules r = op_rules(op);
   Plan pl;
   const int side = s.rows;

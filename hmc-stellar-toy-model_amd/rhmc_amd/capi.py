@@ -27,11 +27,15 @@ STATUS_QLOOP_CAP = 4
 STATUS_REFLECT_F = 8
 STATUS_REFLECT_XY = 16
 STATUS_NEAR_WALL = 32     # a reflection within 1e-12 of its wall
+PEAK_CONVERGED = 256      # how a find_peaks seed stopped (RHMC_PEAK_*, include/rhmc.h)
+PEAK_FAINT = 512
+PEAK_CAP = 1024
 
 OPT_KERNEL = 1            # rhmc_ctx_set_option (include/rhmc.h)
 OPT_MH_FUSED = 2
 OPT_WINDOW_SPLIT = 3        # waves per chain pair in leapfrog_kr (0: by batch size)
 OPT_TABLES = 4              # where WinGG keeps its factor tables (diagnostic, rhmc.h)
+OPT_PEAKS_FUSED = 5         # find_peaks: one-launch descent kernel where it exists
 (TABLES_STREAM, TABLES_STREAM_POISON, TABLES_POOL, TABLES_POOL_POISON, TABLES_POOL_KEEP,
  TABLES_POOL_SYNCFREE, TABLES_POOL_BARRIER) = range(7)
 # RHMC_KERNEL_* values by name
@@ -54,7 +58,8 @@ EXPORTS = ("rhmc_abi_version", "rhmc_device_count", "rhmc_last_error",
            "rhmc_gen_image", "rhmc_gen_image_device", "rhmc_hmc_random",
            "rhmc_hmc_random_device", "rhmc_mh_scheduled", "rhmc_mh_scheduled_device",
            "rhmc_ragged_ok", "rhmc_leapfrog_ragged_device", "rhmc_energy_ragged_device",
-           "rhmc_rows_copy_device", "rhmc_kinetic_rows_device")
+           "rhmc_rows_copy_device", "rhmc_kinetic_rows_device",
+           "rhmc_find_peaks", "rhmc_find_peaks_device")
 ABI_VERSION = 4
 
 V_FLUX_WALL = 1       # rhmc_energy f_pos bits (include/rhmc.h)
@@ -93,6 +98,19 @@ class MhSchedule(ctypes.Structure):
     """Mirror of `rhmc_mh_schedule` (include/rhmc.h): host arrays."""
     _fields_ = [("g_ff2", ctypes.c_void_p), ("beta", ctypes.c_void_p),
                 ("n_g_ff2", ctypes.c_int32), ("n_beta", ctypes.c_int32)]
+
+
+class PeaksOpts(ctypes.Structure):
+    """Mirror of `rhmc_peaks_opts` (include/rhmc.h)."""
+    _fields_ = [("f_lim", ctypes.c_double), ("dt_f_coeff", ctypes.c_double),
+                ("dt_xy_coeff", ctypes.c_double), ("rel_tol", ctypes.c_double),
+                ("n_step", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def make_peaks_opts(f_lim, n_step=1000, dt_f_coeff=1e-1, dt_xy_coeff=1e-1, rel_tol=1e-9):
+    """find_peaks' arguments (samplers.py:129-130; rel_tol is its hard-wired 1e-9)."""
+    return PeaksOpts(float(f_lim), float(dt_f_coeff), float(dt_xy_coeff), float(rel_tol),
+                     int(n_step), 0)
 
 
 def make_schedule(schedule_g_ff2=None, schedule_beta=None):
@@ -189,6 +207,10 @@ def _load():
                                                  vp, ctypes.c_int64, ctypes.c_int32, vp]),
         "rhmc_kinetic_rows_device": (ctypes.c_int, [vp, P(RhmcParams), vp, vp, ctypes.c_int64,
                                                     vp, vp, vp, ctypes.c_int64, vp, vp]),
+        "rhmc_find_peaks": (ctypes.c_int, [vp, P(RhmcParams), P(PeaksOpts), c_dp, ctypes.c_int64,
+                                           c_ip, c_ip, c_dp]),
+        "rhmc_find_peaks_device": (ctypes.c_int, [vp, P(RhmcParams), P(PeaksOpts), vp,
+                                                  ctypes.c_int64, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -524,6 +546,30 @@ class Context:
         if single:
             q2, p2, st = q2[0], p2[0], st[0]
         return (q2, p2, st) if return_status else (q2, p2)
+
+    def find_peaks(self, params, opts, q):
+        """find_peaks' seed descent (rhmc_find_peaks) on seeds q [n, 3] =
+        (f counts, x, y); opts: make_peaks_opts(...).  Returns (q, steps,
+        status, V): the final states, the gradient evaluations, PEAK_* (|
+        STATUS_NONFINITE) and the last V evaluated per seed."""
+        q2 = np.array(q, dtype=np.float64, order="C", copy=True).reshape(-1, 3)
+        n = q2.shape[0]
+        steps = np.zeros(n, np.int32)
+        status = np.zeros(n, np.int32)
+        V = np.zeros(n)
+        _check(_lib.rhmc_find_peaks(self._h, ctypes.byref(params), ctypes.byref(opts), _dptr(q2),
+                                    n, _iptr(steps), _iptr(status), _dptr(V)))
+        return q2, steps, status, V
+
+    def find_peaks_device(self, params, opts, q_ptr, n, steps_ptr=None, status_ptr=None,
+                          V_ptr=None, stream=None):
+        """Device-pointer rhmc_find_peaks (asynchronous on `stream`)."""
+        _check(_lib.rhmc_find_peaks_device(self._h, ctypes.byref(params), ctypes.byref(opts),
+                                           ctypes.c_void_p(q_ptr), int(n),
+                                           ctypes.c_void_p(steps_ptr or 0),
+                                           ctypes.c_void_p(status_ptr or 0),
+                                           ctypes.c_void_p(V_ptr or 0),
+                                           ctypes.c_void_p(stream or 0)))
 
     def gen_image(self, params, q, rows, cols, n_real=0, seed=0, install=False):
         """Model image (n_real=0, gen_model) or n_real Poisson realisations of it

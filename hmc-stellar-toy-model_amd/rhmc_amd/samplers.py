@@ -1,5 +1,7 @@
-"""The reference's older `samplers` API on the sampling path, routed to the
-MI355X engine: `lightsource_gym` with unit-mass HMC (`HMC_random`).
+"""The reference's older `samplers` API, routed to the MI355X engine:
+`lightsource_gym` with its three-stage pipeline — `find_peaks` (seed stars),
+`HMC_find_best_dt` (the step vector, default branch) and unit-mass HMC
+(`HMC_random`).
 
 Mirrors jaekor91/HMC-stellar-toy-model `samplers.py` (file:line per method):
 same class name, attributes (set after construction, like the reference's
@@ -7,10 +9,11 @@ scripts: `gym.Nobjs`, `gym.d = 3 * Nobjs`, `gym.dt = <vector [d]>`), method
 names, argument meaning, global-NumPy-RNG draw order and results.
 
 What runs where:
-  * dVdq, V and the HMC_random trajectories run in librhmc.so
-    (rhmc_gradient kind 0, rhmc_energy without the position check,
-    rhmc_hmc_random).  No CPU fallback.
-  * E, K, p_sample and the MH bookkeeping stay on the host (NumPy), like the
+  * dVdq, V, the HMC_random trajectories and find_peaks' gradient descent
+    of the seeds run in librhmc.so (rhmc_gradient kind 0, rhmc_energy without
+    the position check, rhmc_hmc_random, rhmc_find_peaks).  No CPU fallback.
+  * E, K, p_sample, the MH bookkeeping, find_peaks' seed grid and its merge of
+    near-duplicate peaks (merge_peaks) stay on the host (NumPy), like the
     reference.
 
 Quirks kept on purpose (samplers.py:519-552): the flux-wall flip mask is
@@ -19,13 +22,55 @@ is evaluated with the momentum it started from.  HMC_random requires
 Nchain == 1 (assert, like the reference); HMC_random_batched runs many chains
 at once and, with one chain, draws exactly what HMC_random draws.
 
-Out of scope: find_peaks / HMC_find_best_dt (seed and step-size
-search), RHMC_random_diag / RHMC_random, the GMM testbed and the plots.
+Not built: HMC_find_best_dt's step-size search (default=False; it needs a
+per-star residual image as the background, the kernels take a constant B).
+Out of scope: RHMC_random_diag / RHMC_random, the GMM testbed and
+the plots.
 """
 import numpy as np
 
 from . import capi
-from .photometry import default_exp_setup, gauss_PSF, mag2flux, poisson_realization
+from .photometry import (default_exp_setup, flux2mag, gauss_PSF, mag2flux,
+                         poisson_realization)
+
+
+def seed_grid(num_rows, num_cols, linear_pix_density, f_seed):
+    """samplers.py:168-180: the jittered grid of seeds [Nobjs_tot, 3], two
+    np.random.randn() draws per seed in the reference's order and its index
+    idx = i * Nobjs_row + j."""
+    Nobjs_row = int(linear_pix_density * num_rows) - 1
+    Nobjs_col = int(linear_pix_density * num_cols) - 1
+    grid_spacing = 1 / float(linear_pix_density)
+    q_seed = np.zeros((Nobjs_row * Nobjs_col, 3), dtype=float)
+    for i in range(Nobjs_row):
+        for j in range(Nobjs_col):
+            idx = i * Nobjs_row + j
+            x = grid_spacing * (i + 0.5 + 0.1 * np.random.randn())
+            y = grid_spacing * (j + 0.5 + 0.1 * np.random.randn())
+            q_seed[idx] = np.array([f_seed, x, y])
+    return q_seed
+
+
+def merge_peaks(q_seed, flux_to_count, dr_tol=1., dmag_tol=0.5):
+    """samplers.py:232-252: the sequential merge of near-duplicate peaks.  The
+    first remaining peak is kept and every later one within dr_tol pixels AND
+    dmag_tol magnitudes of it is dropped, until none remains.  q_seed [n, 3]
+    with n >= 1; returns the kept peaks [m, 3] in order."""
+    q_seed = np.asarray(q_seed, dtype=float).reshape(-1, 3)
+    final = []
+    while True:
+        q_ref = q_seed[0]
+        final.append(q_ref)
+        q_seed = q_seed[1:, :]
+        dist_sq = (q_seed[:, 1] - q_ref[1]) ** 2 + (q_seed[:, 2] - q_ref[2]) ** 2
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mag_seed = flux2mag(q_seed[:, 0] / flux_to_count)
+            mag_ref = flux2mag(q_ref[0] / flux_to_count)
+            ibool = np.logical_or(dist_sq > dr_tol ** 2, np.abs(mag_ref - mag_seed) > dmag_tol)
+        q_seed = q_seed[ibool]
+        if q_seed.shape[0] == 0:
+            break
+    return np.vstack(final)
 
 
 class lightsource_gym(object):
@@ -53,6 +98,8 @@ class lightsource_gym(object):
         self.d = None
         self.f_lim = 0.
         self.q_seed = None
+        self.peak_steps = None   # find_peaks diagnostics, per grid seed (pre-merge)
+        self.peak_status = None
         self.device = 0
 
     # ---------------------------------------------------------------- data
@@ -134,6 +181,62 @@ class lightsource_gym(object):
         q_new = q_old + dt * p_half
         p_new = p_half - dt * self.dVdq(q_new) / 2.
         return p_new, q_new
+
+    # ---------------------------------------------------------------- seeds
+    def find_peaks(self, linear_pix_density=0.2, dr_tol=1., dmag_tol=0.5, mag_lim=None,
+                   Nstep=1000, dt_f_coeff=1e-1, dt_xy_coeff=1e-1, no_perturb=False):
+        """samplers.py:129-254.  Seeds on a jittered grid (the global NumPy RNG
+        draws the jitter), each run through up to Nstep steps of gradient
+        descent on the one-star potential against the pure-background model
+        (on the GPU, rhmc_find_peaks); seeds that turn fainter than the limit
+        disappear, near-duplicates are merged.  Sets q_seed [n, 3]; peak_steps
+        / peak_status keep the per-seed step counts and capi.PEAK_* words."""
+        if self.num_rows is None or self.D is None:
+            print("The image must be specified first.")
+            assert False
+        if mag_lim is None:
+            mag_lim = self.mB - 1.
+        f_lim = mag2flux(mag_lim) * self.flux_to_count
+        f_seed = mag2flux(mag_lim - 0.5) * self.flux_to_count
+        q_seed = seed_grid(self.num_rows, self.num_cols, linear_pix_density, f_seed)
+        if no_perturb:
+            self.q_seed = q_seed
+            return
+        opts = capi.make_peaks_opts(f_lim, n_step=Nstep, dt_f_coeff=dt_f_coeff,
+                                    dt_xy_coeff=dt_xy_coeff, rel_tol=1e-9)
+        q_seed, steps, status, _ = self._context().find_peaks(self._params(), opts, q_seed)
+        self.peak_steps = steps
+        self.peak_status = status
+        q_seed = q_seed[(status & capi.PEAK_FAINT) == 0]
+        if q_seed.shape[0] == 0:
+            self.q_seed = q_seed
+            print("No peaks were found.")
+            return
+        self.q_seed = merge_peaks(q_seed, self.flux_to_count, dr_tol, dmag_tol)
+
+    def HMC_find_best_dt(self, q_model_0=None, steps_min=10, steps_max=50, Niter_per_trial=10,
+                         Ntrial=10, dt_f_coeff=1., dt_xy_coeff=10., default=False,
+                         A_target_f=0.9, A_target_xy=0.5):
+        """samplers.py:257-303, the default=True branch: Nobjs, d and the step
+        vector dt = (dt_f_coeff f, dt_xy_coeff / f, dt_xy_coeff / f) per star.
+        The search (default=False, :306-456) is not built."""
+        if q_model_0 is None:
+            print("Use found seeds for inference.")
+            q_model_0 = self.q_seed
+        q_model_0 = np.asarray(q_model_0, dtype=float).reshape(-1, 3)
+        self.Nobjs = q_model_0.shape[0]
+        self.d = self.Nobjs * 3
+        self.dt = np.zeros(self.d)
+        if not default:
+            raise NotImplementedError(
+                "HMC_find_best_dt(default=False): the step-size search perturbs one star "
+                "against the residual image of the others as its background, and the "
+                "kernels take a constant background B; use default=True")
+        for i in range(self.Nobjs):
+            f0, x0, y0 = q_model_0[i]
+            dt_xy = dt_xy_coeff / f0
+            dt_f = dt_f_coeff * f0
+            self.dt[3 * i:3 * i + 3] = np.array([dt_f, dt_xy, dt_xy])
 
     # ------------------------------------------------------------- sampling
     def _trajectories(self, q, p, steps):

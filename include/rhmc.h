@@ -46,6 +46,11 @@
  *       device-resident ragged sets: the reversible-jump iterations of
  *       run_RHMC (:1018-1187), whose chains change K by births, deaths,
  *       splits and merges (librhmc_rj.so keeps them in HBM between phases).
+ *   rhmc_find_peaks / rhmc_find_peaks_device
+ *       samplers.lightsource_gym.find_peaks' gradient descent of the grid
+ *       seeds (samplers.py:190-221) on V_single / dVdq_single (:77-127)
+ *       against the pure-background model; the seed grid (:157-180) and the
+ *       merge of near-duplicates (:232-252) stay on the host.
  *   rhmc_params
  *       the instance attributes the step reads: dt, g_xx,
  *       g_ff, g_ff2, g0, g1, g2, B_count, f_lim, mB (-> f_low),
@@ -112,6 +117,12 @@ enum {
  * chain can legitimately reflect the other way on a last-bit difference
  * (SURVEY §8(c)), so callers report these chains separately. */
 #define RHMC_STATUS_NEAR_WALL  32u
+/* How a seed of rhmc_find_peaks stopped: exactly one of the three per seed,
+ * in bits the step's status bits above do not use (RHMC_STATUS_NONFINITE may
+ * come with them). */
+#define RHMC_PEAK_CONVERGED  256u  /* |(V - V_prev)/V_prev| < rel_tol (samplers.py:215) */
+#define RHMC_PEAK_FAINT      512u  /* f < f_lim after an update (:209-211)              */
+#define RHMC_PEAK_CAP       1024u  /* n_step steps without either                       */
 
 /* Instance state read by the step (POD; all fp64 except the flags). */
 typedef struct rhmc_params {
@@ -182,12 +193,17 @@ typedef struct rhmc_ctx rhmc_ctx;
  *   (a reused pool block is zeroed while the launch that
  *   received it runs); only -DRHMC_TABLE_DIAG builds accept them, the library
  *   returns RHMC_ERR_UNSUPPORTED.
+ * RHMC_OPT_PEAKS_FUSED: 1 (default) = rhmc_find_peaks runs the one-launch
+ *   descent kernel where it exists (32/48/64-px images, a PSF narrow enough
+ *   for the 28-px window, no forced per-wave family), 0 = always the stepwise
+ *   path (gradient / update / energy / update launches per step).
  */
 enum {
   RHMC_OPT_KERNEL = 1,
   RHMC_OPT_MH_FUSED = 2,
   RHMC_OPT_WINDOW_SPLIT = 3,
-  RHMC_OPT_TABLES = 4
+  RHMC_OPT_TABLES = 4,
+  RHMC_OPT_PEAKS_FUSED = 5
 };
 enum {
   RHMC_TABLES_STREAM = 0,
@@ -418,6 +434,41 @@ int rhmc_gen_image(rhmc_ctx* ctx, const rhmc_params* P, const double* q, int32_t
 int rhmc_gen_image_device(rhmc_ctx* ctx, const rhmc_params* P, const double* d_q, int32_t K,
                           int32_t rows, int32_t cols, int32_t n_real, uint64_t seed,
                           double* d_out, void* stream);
+
+/*
+ * samplers.lightsource_gym.find_peaks' seed descent (samplers.py:190-221):
+ * every seed q[i] = (f, x, y) (counts, pixels) runs gradient descent on the
+ * one-star potential V = -sum(D ln Lambda - Lambda), Lambda = B + f PSF over
+ * the whole image (V_single :121-127, dVdq_single :93-101), for at most
+ * n_step steps:
+ *   dt_f = f dt_f_coeff, dt_xy = dt_xy_coeff / f   (from f before the update)
+ *   f -= dV/df dt_f, x -= dV/dx dt_xy, y -= dV/dy dt_xy
+ *   f < f_lim: RHMC_PEAK_FAINT (the state keeps the update)
+ *   |(V - V_prev)/V_prev| < rel_tol: RHMC_PEAK_CONVERGED (the reference: 1e-9)
+ * and RHMC_PEAK_CAP after n_step steps.  There is no other confinement.  A
+ * seed whose state turns non-finite passes neither test: it ends with
+ * steps = n_step and RHMC_PEAK_CAP | RHMC_STATUS_NONFINITE.  Only P->B_count
+ * and P->fwhm_pix are read from P (no prior, no repulsion); f_lim is opts'.
+ * q [n][3] is updated in place; steps [n] (gradient evaluations), status [n]
+ * and V [n] (the last V evaluated: the initial V for a seed faint after its
+ * first step) are nullable.  n = 0 is a no-op.  RHMC_ERR_ARG: NULL ctx, q or
+ * opts, n < 0, n_step < 0 or > 10^6, a non-finite coefficient.
+ */
+typedef struct rhmc_peaks_opts {
+  double f_lim;        /* flux below which a seed disappears (counts)        */
+  double dt_f_coeff;   /* find_peaks' dt_f_coeff                             */
+  double dt_xy_coeff;  /* find_peaks' dt_xy_coeff                            */
+  double rel_tol;      /* relative change of V that ends the descent         */
+  int32_t n_step;      /* find_peaks' Nstep                                  */
+  int32_t reserved;    /* must be 0                                          */
+} rhmc_peaks_opts;
+int rhmc_find_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* opts, double* q,
+                    int64_t n, int32_t* steps, int32_t* status, double* V);
+/* Device pointers, asynchronous on `stream` (the stepwise path may wait for
+ * the stream every 16 steps to stop once every seed has). */
+int rhmc_find_peaks_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* opts,
+                           double* d_q, int64_t n, int32_t* d_steps, int32_t* d_status,
+                           double* d_V, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@
 #include "rhmc_mhk1.hpp"
 #include "rhmc_mhpk.hpp"
 #include "rhmc_peaks.hpp"
+#include "rhmc_dt.hpp"
 #include "rhmc_pixk.hpp"
 #include "rhmc_wave.hpp"
 #include "rhmc_windowed.hpp"
@@ -78,6 +79,9 @@ struct rhmc_ctx {
   int window_split = 0;            // RHMC_OPT_WINDOW_SPLIT (0: by batch size)
   int peaks_fused = 1;             // RHMC_OPT_PEAKS_FUSED
   int32_t* h_pin = nullptr;        // pinned word: find_peaks' stepwise path polls through it
+  int dt_lanes = 0;                // RHMC_OPT_DT_LANES
+  void* dt_tab = nullptr;          // dt_trials' factor tables of the global-memory path
+  size_t dt_tab_bytes = 0;
   int table_mode = RHMC_TABLES_STREAM;  // RHMC_OPT_TABLES (diagnostic modes, rhmc.h)
   // WinGG factor tables, one buffer per stream (work_tables).  A launch holds a
   // lease (shared_ptr) on its buffer from the lookup until the launch is
@@ -142,6 +146,49 @@ int check_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* o, c
   return RHMC_OK;
 }
 
+// The checks the two dt_trials entry points share (n == 0 after them: a
+// no-op), arguments before the context like check_peaks.
+int check_dt(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opts* o, const double* bg,
+             int32_t n_bg, const int32_t* bg_index, const double* q0, const double* dt, int64_t n,
+             const double* z, const int32_t* steps, const double* lnu,
+             const uint64_t* stream_id, bool host_call) {
+  if (!P) return fail(RHMC_ERR_ARG, "params is NULL");
+  if (!o) return fail(RHMC_ERR_ARG, "opts is NULL");
+  if (n < 0) return fail(RHMC_ERR_ARG, "n < 0");
+  if (n > ((int64_t)1 << 31)) return fail(RHMC_ERR_ARG, "n too large (2^31 tasks at most)");
+  if (o->reserved[0] != 0 || o->reserved[1] != 0)
+    return fail(RHMC_ERR_ARG, "opts.reserved must be 0");
+  if (o->n_iter < 1 || o->n_iter > 1024)
+    return fail(RHMC_ERR_ARG, "opts.n_iter must be in [1, 1024]");
+  if (o->grad != RHMC_DT_GRAD_REFERENCE && o->grad != RHMC_DT_GRAD_FULL)
+    return fail(RHMC_ERR_ARG, "opts.grad must be RHMC_DT_GRAD_REFERENCE or RHMC_DT_GRAD_FULL");
+  const int n_draws = (z != nullptr) + (steps != nullptr) + (lnu != nullptr);
+  if (n_draws != 0 && n_draws != 3)
+    return fail(RHMC_ERR_ARG, "z, steps and lnu: pass all three or none");
+  if (n_draws == 0) {
+    if (!(o->steps_min >= 0 && o->steps_min < o->steps_max && o->steps_max <= 65536))
+      return fail(RHMC_ERR_ARG, "opts: 0 <= steps_min < steps_max <= 65536 for device draws");
+    if (!stream_id) return fail(RHMC_ERR_ARG, "stream_id is NULL (device draws)");
+  }
+  if (!bg) return fail(RHMC_ERR_ARG, "bg is NULL");
+  if (n_bg < 1) return fail(RHMC_ERR_ARG, "n_bg < 1");
+  if (!bg_index) return fail(RHMC_ERR_ARG, "bg_index is NULL");
+  if (!q0) return fail(RHMC_ERR_ARG, "q0 is NULL");
+  if (!dt) return fail(RHMC_ERR_ARG, "dt is NULL");
+  if (host_call) {                                 // (the device entry point clamps these)
+    for (int64_t t = 0; t < n; ++t)
+      if (bg_index[t] < 0 || bg_index[t] >= n_bg)
+        return fail(RHMC_ERR_ARG, "bg_index[" + std::to_string(t) + "] outside [0, n_bg)");
+    if (steps)
+      for (int64_t r = 0; r < n * o->n_iter; ++r)
+        if (steps[r] < 0 || steps[r] > 65535)
+          return fail(RHMC_ERR_ARG, "steps[" + std::to_string(r) + "] outside 0..65535");
+  }
+  if (!ctx) return fail(RHMC_ERR_ARG, "ctx is NULL");
+  if (n > 0 && !ctx->d_D) return fail(RHMC_ERR_ARG, "no image uploaded");
+  return RHMC_OK;
+}
+
 // Staging of the host-buffer entry points: the buffers of one call as parts
 // of ctx->scratch, each aligned to 256 bytes.  add() lists a buffer, run()
 // sizes the scratch, uploads the inputs, calls the launch, downloads the
@@ -155,7 +202,7 @@ struct Staging {
     int dir;
   };
   rhmc_ctx* ctx;
-  Part part[8];
+  Part part[16];
   int n = 0;
   size_t total = 0;
 
@@ -311,6 +358,11 @@ int rhmc_ctx_set_option(rhmc_ctx* ctx, int32_t option, int32_t value) {
         return fail(RHMC_ERR_ARG, "RHMC_OPT_PEAKS_FUSED must be 0 or 1");
       ctx->peaks_fused = value;
       return RHMC_OK;
+    case RHMC_OPT_DT_LANES:
+      if (value != 0 && value != 64 && value != 256)
+        return fail(RHMC_ERR_ARG, "RHMC_OPT_DT_LANES must be 0, 64 or 256");
+      ctx->dt_lanes = value;
+      return RHMC_OK;
     case RHMC_OPT_WINDOW_SPLIT:
       if (value != 0 && value != 1 && value != 2 && value != 4)
         return fail(RHMC_ERR_ARG, "RHMC_OPT_WINDOW_SPLIT must be 0, 1, 2 or 4");
@@ -342,6 +394,7 @@ int rhmc_ctx_get_option(rhmc_ctx* ctx, int32_t option, int32_t* value) {
     case RHMC_OPT_WINDOW_SPLIT: *value = ctx->window_split; return RHMC_OK;
     case RHMC_OPT_TABLES: *value = ctx->table_mode; return RHMC_OK;
     case RHMC_OPT_PEAKS_FUSED: *value = ctx->peaks_fused; return RHMC_OK;
+    case RHMC_OPT_DT_LANES: *value = ctx->dt_lanes; return RHMC_OK;
     default: return fail(RHMC_ERR_ARG, "unknown option " + std::to_string(option));
   }
 }
@@ -362,6 +415,7 @@ void rhmc_ctx_destroy(rhmc_ctx* ctx) {
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->mh_scratch) (void)hipFree(ctx->mh_scratch);
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
+  if (ctx->dt_tab) (void)hipFree(ctx->dt_tab);
   if (!ctx->tabs.empty() || !ctx->kept.empty())
     (void)hipDeviceSynchronize();   // tables may serve user streams
   for (auto& t : ctx->tabs)
@@ -693,6 +747,62 @@ int rhmc_find_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* 
   return st.run([&] {
     return launch_find_peaks(ctx, P, opts, st.dev<double>(iq), n, st.dev<int32_t>(is),
                              st.dev<int32_t>(it), st.dev<double>(iV), ctx->stream);
+  });
+}
+
+int rhmc_dt_trials_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opts* opts,
+                          const double* d_bg, int32_t n_bg, const int32_t* d_bg_index,
+                          const double* d_q0, const double* d_dt, const int32_t* d_flux_only,
+                          int64_t n, const double* d_z, const int32_t* d_steps,
+                          const double* d_lnu, uint64_t seed, const uint64_t* d_stream_id,
+                          int32_t* d_n_accept, const rhmc_dt_record* rec, void* stream) {
+  if (int rc = check_dt(ctx, P, opts, d_bg, n_bg, d_bg_index, d_q0, d_dt, n, d_z, d_steps, d_lnu,
+                        d_stream_id, false))
+    return rc;
+  if (n == 0) return RHMC_OK;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  const DtCall k{d_bg, n_bg, d_bg_index, d_q0, d_dt, d_flux_only, n, d_z, d_steps, d_lnu, seed,
+                 d_stream_id, d_n_accept, rec ? *rec : rhmc_dt_record{}};
+  return launch_dt_trials(ctx, P, opts, k, s);
+}
+
+int rhmc_dt_trials(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opts* opts,
+                   const double* bg, int32_t n_bg, const int32_t* bg_index, const double* q0,
+                   const double* dt, const int32_t* flux_only, int64_t n, const double* z,
+                   const int32_t* steps, const double* lnu, uint64_t seed,
+                   const uint64_t* stream_id, int32_t* n_accept, const rhmc_dt_record* rec) {
+  if (int rc = check_dt(ctx, P, opts, bg, n_bg, bg_index, q0, dt, n, z, steps, lnu, stream_id,
+                        true))
+    return rc;
+  if (n == 0) return RHMC_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t npix = (size_t)ctx->rows * ctx->cols, ni = (size_t)n * opts->n_iter;
+  const rhmc_dt_record r = rec ? *rec : rhmc_dt_record{};
+  Staging st(ctx);  // an array not given has no part (NULL to the kernel)
+  const int ibg = st.add(bg, (size_t)n_bg * npix * sizeof(double), Staging::kIn);
+  const int ibi = st.add(bg_index, (size_t)n * sizeof(int32_t), Staging::kIn);
+  const int iq0 = st.add(q0, (size_t)n * 3 * sizeof(double), Staging::kIn);
+  const int idt = st.add(dt, (size_t)n * 3 * sizeof(double), Staging::kIn);
+  const int ifo = st.add(flux_only, flux_only ? (size_t)n * sizeof(int32_t) : 0, Staging::kIn);
+  const int iz = st.add(z, z ? ni * 3 * sizeof(double) : 0, Staging::kIn);
+  const int ist = st.add(steps, steps ? ni * sizeof(int32_t) : 0, Staging::kIn);
+  const int ilu = st.add(lnu, lnu ? ni * sizeof(double) : 0, Staging::kIn);
+  const int isi = st.add(stream_id, stream_id ? (size_t)n * sizeof(uint64_t) : 0, Staging::kIn);
+  const int ina = st.add(n_accept, n_accept ? (size_t)n * sizeof(int32_t) : 0, Staging::kOut);
+  const int rdE = st.add(r.dE, r.dE ? ni * sizeof(double) : 0, Staging::kOut);
+  const int rac = st.add(r.accept, r.accept ? ni * sizeof(int32_t) : 0, Staging::kOut);
+  const int rq = st.add(r.q, r.q ? ni * 3 * sizeof(double) : 0, Staging::kOut);
+  const int rz = st.add(r.z, r.z ? ni * 3 * sizeof(double) : 0, Staging::kOut);
+  const int rst = st.add(r.steps, r.steps ? ni * sizeof(int32_t) : 0, Staging::kOut);
+  const int rlu = st.add(r.lnu, r.lnu ? ni * sizeof(double) : 0, Staging::kOut);
+  return st.run([&] {
+    const DtCall k{st.dev<double>(ibg), n_bg, st.dev<int32_t>(ibi), st.dev<double>(iq0),
+                   st.dev<double>(idt), st.dev<int32_t>(ifo), n, st.dev<double>(iz),
+                   st.dev<int32_t>(ist), st.dev<double>(ilu), seed, st.dev<uint64_t>(isi),
+                   st.dev<int32_t>(ina),
+                   rhmc_dt_record{st.dev<double>(rdE), st.dev<int32_t>(rac), st.dev<double>(rq),
+                                  st.dev<double>(rz), st.dev<int32_t>(rst), st.dev<double>(rlu)}};
+    return launch_dt_trials(ctx, P, opts, k, ctx->stream);
   });
 }
 

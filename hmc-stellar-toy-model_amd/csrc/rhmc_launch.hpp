@@ -10,7 +10,8 @@ namespace {
 
 SelectIn select_in(const rhmc_ctx* ctx) {
   return SelectIn{ctx->rows,  ctx->cols,   ctx->img_f32,  ctx->max_lds,     ctx->n_cu,
-                  ctx->kernel, ctx->mh_fused, ctx->window_split, ctx->peaks_fused};
+                  ctx->kernel, ctx->mh_fused, ctx->window_split, ctx->peaks_fused,
+                  ctx->dt_lanes};
 }
 
 // The plan of one call; an unsupported configuration is the error here.
@@ -1138,6 +1139,94 @@ int launch_find_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts
     using DT = typename decltype(dt)::type;
     hipLaunchKernelGGL((peaks_k1_tiledr<decltype(img)::value, DT>), grid, block, lds, s, k);
   });
+}
+
+// ---------------------------------------------------------------------------
+// HMC_find_best_dt's trials (rhmc_dt.hpp)
+// ---------------------------------------------------------------------------
+
+// The arguments both entry points share; the record's members may be NULL.
+struct DtCall {
+  const double* bg;
+  int32_t n_bg;
+  const int32_t* bg_index;
+  const double *q0, *dt;
+  const int32_t* flux_only;
+  int64_t n;
+  const double* z;
+  const int32_t* steps;
+  const double* lnu;
+  uint64_t seed;
+  const uint64_t* stream_id;
+  int32_t* n_accept;
+  rhmc_dt_record rec;
+};
+
+template <int LANES, int PPL>
+void launch_dt_kernel(const DtArgs& a, unsigned blocks, hipStream_t s) {
+  const size_t lds = PPL > 0 ? (size_t)(2 * a.side + 1) * sizeof(double2) : 0;
+  hipLaunchKernelGGL((dt_trials_kernel<LANES, PPL>), dim3(blocks), dim3(LANES), lds, s, a);
+}
+
+int launch_dt_trials(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opts* o, const DtCall& k,
+                     hipStream_t s) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  const DtPlan pl = select_dt(select_in(ctx));
+  if (pl.message) return fail(RHMC_ERR_UNSUPPORTED, pl.message);
+  HIP_TRY(hipSetDevice(ctx->device));
+  DtArgs a;
+  a.D = ctx->d_D;
+  a.bg = k.bg;
+  a.bg_index = k.bg_index;
+  a.q0 = k.q0;
+  a.dt = k.dt;
+  a.flux_only = k.flux_only;
+  a.z = k.z;
+  a.steps = k.steps;
+  a.lnu = k.lnu;
+  a.stream_id = k.stream_id;
+  a.n_accept = k.n_accept;
+  a.r_dE = k.rec.dE;
+  a.r_accept = k.rec.accept;
+  a.r_q = k.rec.q;
+  a.r_z = k.rec.z;
+  a.r_steps = k.rec.steps;
+  a.r_lnu = k.rec.lnu;
+  a.gtab = nullptr;
+  a.n = k.n;
+  a.seed = k.seed;
+  a.n_iter = o->n_iter;
+  a.grad = o->grad;
+  a.steps_min = o->steps_min;
+  a.steps_max = o->steps_max;
+  a.side = ctx->rows;
+  a.n_bg = k.n_bg;
+  a.inv_two_sig2 = c.inv_two_sig2;
+  a.inv_norm = c.inv_norm;
+  a.inv_var = c.inv_var;
+  const unsigned blocks = (unsigned)std::min<int64_t>(k.n, pl.blocks_cap);
+  if (pl.ppl == 0) {                               // the workgroups' factor tables
+    const size_t need = (size_t)blocks * (2 * (size_t)a.side + 1) * sizeof(double2);
+    if (grow(&ctx->dt_tab, &ctx->dt_tab_bytes, need) == RHMC_ERR_NOMEM)
+      return fail(RHMC_ERR_NOMEM, "hipMalloc of the dt_trials factor tables failed");
+    a.gtab = (double2*)ctx->dt_tab;
+  }
+  if (pl.lanes == 256) {
+    switch (pl.ppl) {
+      case 4: launch_dt_kernel<256, 4>(a, blocks, s); break;
+      case 9: launch_dt_kernel<256, 9>(a, blocks, s); break;
+      case 16: launch_dt_kernel<256, 16>(a, blocks, s); break;
+      default: launch_dt_kernel<256, 0>(a, blocks, s); break;
+    }
+  } else {
+    switch (pl.ppl) {
+      case 16: launch_dt_kernel<64, 16>(a, blocks, s); break;
+      default: launch_dt_kernel<64, 0>(a, blocks, s); break;
+    }
+  }
+  return launch_status();
 }
 
 // Model image / Poisson realisations (rhmc_datagen.hpp) into d_out

@@ -80,6 +80,7 @@ struct SelectIn {
   int mh_fused = 1;                // RHMC_OPT_MH_FUSED
   int window_split = 0;            // RHMC_OPT_WINDOW_SPLIT (0: by batch size)
   int peaks_fused = 1;             // RHMC_OPT_PEAKS_FUSED
+  int dt_lanes = 0;                // RHMC_OPT_DT_LANES (0: the rule's choice)
 };
 
 enum class Op { Step, Integrate, HmcRandom, Energy, Gradient, MhFused, Peaks };
@@ -285,6 +286,41 @@ inline Plan select_peaks(const SelectIn& s, double inv_two_sig2) {
     pl.family = Family::RegWin1;
     pl.f32 = s.img_f32;
   }
+  return pl;
+}
+
+// The trial kernel of HMC_find_best_dt's search (rhmc_dt.hpp,
+// dt_trials_kernel<lanes, ppl>): one task per workgroup of `lanes` lanes over
+// the whole image.  Square sides 16..64 keep the lane's pixels of D and M in
+// registers, ppl of each: ceil(side^2 / lanes) rounded up to an instantiated
+// size (256 lanes: 4 / 9 / 16 for sides <= 32 / 48 / 64; 64 lanes: 16 for sides
+// <= 32 only, the 36 pixels of D and of M per lane of a 48-px image spill: 276
+// bytes of scratch per lane in the build that tried).  Every other side reads
+// the pixels from global memory (ppl = 0) with factor tables in a global
+// buffer, `blocks_cap` workgroups at most.  Lanes per task: 256
+// unless RHMC_OPT_DT_LANES says 64 (the A/B of DESIGN.md section 4e); the
+// calls that matter have one task per star and are bound by the serial chain
+// of gradients, which 256 lanes make shorter.
+struct DtPlan {
+  int lanes = 256;
+  int ppl = 0;           // pixels per lane in registers, 0: global memory
+  int blocks_cap = 0;    // most workgroups of one launch
+  const char* message = nullptr;   // set: RHMC_ERR_UNSUPPORTED
+};
+
+inline DtPlan select_dt(const SelectIn& s) {
+  DtPlan pl;
+  if (s.rows != s.cols || s.rows < 1) {
+    pl.message = "dt_trials needs a square image";
+    return pl;
+  }
+  const int side = s.rows;
+  pl.lanes = s.dt_lanes == 64 ? 64 : 256;
+  if (side >= 16 && side <= 64) {
+    if (pl.lanes == 256) pl.ppl = side <= 32 ? 4 : (side <= 48 ? 9 : 16);
+    else pl.ppl = side <= 32 ? 16 : 0;
+  }
+  pl.blocks_cap = pl.ppl ? 65536 : 4096;
   return pl;
 }
 

@@ -36,6 +36,9 @@ OPT_MH_FUSED = 2
 OPT_WINDOW_SPLIT = 3        # waves per chain pair in leapfrog_kr (0: by batch size)
 OPT_TABLES = 4              # where WinGG keeps its factor tables (diagnostic, rhmc.h)
 OPT_PEAKS_FUSED = 5         # find_peaks: one-launch descent kernel where it exists
+OPT_DT_LANES = 6            # dt_trials: lanes per task (0: the library's choice, 64, 256)
+DT_GRAD_REFERENCE = 0       # rhmc_dt_opts.grad (RHMC_DT_GRAD_*, include/rhmc.h)
+DT_GRAD_FULL = 1
 (TABLES_STREAM, TABLES_STREAM_POISON, TABLES_POOL, TABLES_POOL_POISON, TABLES_POOL_KEEP,
  TABLES_POOL_SYNCFREE, TABLES_POOL_BARRIER) = range(7)
 # RHMC_KERNEL_* values by name
@@ -59,7 +62,8 @@ EXPORTS = ("rhmc_abi_version", "rhmc_device_count", "rhmc_last_error",
            "rhmc_hmc_random_device", "rhmc_mh_scheduled", "rhmc_mh_scheduled_device",
            "rhmc_ragged_ok", "rhmc_leapfrog_ragged_device", "rhmc_energy_ragged_device",
            "rhmc_rows_copy_device", "rhmc_kinetic_rows_device",
-           "rhmc_find_peaks", "rhmc_find_peaks_device")
+           "rhmc_find_peaks", "rhmc_find_peaks_device",
+           "rhmc_dt_trials", "rhmc_dt_trials_device")
 ABI_VERSION = 4
 
 V_FLUX_WALL = 1       # rhmc_energy f_pos bits (include/rhmc.h)
@@ -111,6 +115,27 @@ def make_peaks_opts(f_lim, n_step=1000, dt_f_coeff=1e-1, dt_xy_coeff=1e-1, rel_t
     """find_peaks' arguments (samplers.py:129-130; rel_tol is its hard-wired 1e-9)."""
     return PeaksOpts(float(f_lim), float(dt_f_coeff), float(dt_xy_coeff), float(rel_tol),
                      int(n_step), 0)
+
+
+class DtOpts(ctypes.Structure):
+    """Mirror of `rhmc_dt_opts` (include/rhmc.h)."""
+    _fields_ = [("n_iter", ctypes.c_int32), ("grad", ctypes.c_int32),
+                ("steps_min", ctypes.c_int32), ("steps_max", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 2)]
+
+
+class DtRecord(ctypes.Structure):
+    """Mirror of `rhmc_dt_record` (include/rhmc.h)."""
+    _fields_ = [("dE", ctypes.c_void_p), ("accept", ctypes.c_void_p), ("q", ctypes.c_void_p),
+                ("z", ctypes.c_void_p), ("steps", ctypes.c_void_p), ("lnu", ctypes.c_void_p)]
+
+
+def make_dt_opts(n_iter=10, grad=DT_GRAD_REFERENCE, steps_min=10, steps_max=50):
+    """HMC_find_best_dt's Niter_per_trial, the gradient form ("reference" /
+    "full" or a DT_GRAD_* value) and the range of the device's step draws."""
+    if isinstance(grad, str):
+        grad = {"reference": DT_GRAD_REFERENCE, "full": DT_GRAD_FULL}[grad]
+    return DtOpts(int(n_iter), int(grad), int(steps_min), int(steps_max), (0, 0))
 
 
 def make_schedule(schedule_g_ff2=None, schedule_beta=None):
@@ -211,6 +236,12 @@ def _load():
                                            c_ip, c_ip, c_dp]),
         "rhmc_find_peaks_device": (ctypes.c_int, [vp, P(RhmcParams), P(PeaksOpts), vp,
                                                   ctypes.c_int64, vp, vp, vp, vp]),
+        "rhmc_dt_trials": (ctypes.c_int, [vp, P(RhmcParams), P(DtOpts), vp, ctypes.c_int32, vp, vp,
+                                          vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_uint64, vp,
+                                          vp, P(DtRecord)]),
+        "rhmc_dt_trials_device": (ctypes.c_int, [vp, P(RhmcParams), P(DtOpts), vp, ctypes.c_int32,
+                                                 vp, vp, vp, vp, ctypes.c_int64, vp, vp, vp,
+                                                 ctypes.c_uint64, vp, vp, P(DtRecord), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -570,6 +601,70 @@ class Context:
                                            ctypes.c_void_p(status_ptr or 0),
                                            ctypes.c_void_p(V_ptr or 0),
                                            ctypes.c_void_p(stream or 0)))
+
+    def dt_trials(self, params, opts, bg, bg_index, q0, dt, flux_only=None, z=None, steps=None,
+                  lnu=None, seed=0, stream_id=None, record=False):
+        """The trials of HMC_find_best_dt's search (rhmc_dt_trials): task t
+        starts at q0[t] with the steps dt[t] against the background image
+        bg[bg_index[t]]; opts: make_dt_opts(...).  Draws: z [n, n_iter, 3],
+        steps [n, n_iter] and lnu [n, n_iter] (all three), or none and
+        stream_id [n] for the device's Philox draws under `seed`.  Returns
+        n_accept [n], with record=True (n_accept, dict of dE, accept, q, z,
+        steps, lnu per iteration)."""
+        bg = np.ascontiguousarray(bg, np.float64)
+        if bg.ndim == 2:
+            bg = bg[None]
+        if bg.ndim != 3 or bg.shape[1:] != tuple(self.shape):
+            raise ValueError("bg must be [n_bg, %d, %d]" % tuple(self.shape))
+        q0 = np.ascontiguousarray(q0, np.float64).reshape(-1, 3)
+        n = q0.shape[0]
+        ni = opts.n_iter
+        dt = np.ascontiguousarray(dt, np.float64).reshape(n, 3)
+        bg_index = np.ascontiguousarray(bg_index, np.int32).reshape(n)
+        keep = [bg, q0, dt, bg_index]
+
+        def arr(a, dtype, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype).reshape(shape)
+            keep.append(a)
+            return a
+
+        def ptr(a):
+            return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+        flux_only = arr(flux_only, np.int32, (n,))
+        z = arr(z, np.float64, (n, ni, 3))
+        steps = arr(steps, np.int32, (n, ni))
+        lnu = arr(lnu, np.float64, (n, ni))
+        stream_id = arr(stream_id, np.uint64, (n,))
+        n_accept = np.zeros(n, np.int32)
+        rec, out = None, None
+        if record:
+            out = dict(dE=np.zeros((n, ni)), accept=np.zeros((n, ni), np.int32),
+                       q=np.zeros((n, ni, 3)), z=np.zeros((n, ni, 3)),
+                       steps=np.zeros((n, ni), np.int32), lnu=np.zeros((n, ni)))
+            rec = DtRecord(*[out[k].ctypes.data for k in ("dE", "accept", "q", "z", "steps", "lnu")])
+        _check(_lib.rhmc_dt_trials(
+            self._h, ctypes.byref(params), ctypes.byref(opts), ptr(bg), bg.shape[0], ptr(bg_index),
+            ptr(q0), ptr(dt), ptr(flux_only), n, ptr(z), ptr(steps), ptr(lnu),
+            ctypes.c_uint64(int(seed)), ptr(stream_id), ptr(n_accept),
+            None if rec is None else ctypes.byref(rec)))
+        del keep
+        return (n_accept, out) if record else n_accept
+
+    def dt_trials_device(self, params, opts, bg_ptr, n_bg, bg_index_ptr, q0_ptr, dt_ptr, n,
+                         flux_only_ptr=None, z_ptr=None, steps_ptr=None, lnu_ptr=None, seed=0,
+                         stream_id_ptr=None, n_accept_ptr=None, record=None, stream=None):
+        """Device-pointer rhmc_dt_trials (asynchronous on `stream`); record: a
+        DtRecord of device pointers or None."""
+        vp = ctypes.c_void_p
+        _check(_lib.rhmc_dt_trials_device(
+            self._h, ctypes.byref(params), ctypes.byref(opts), vp(bg_ptr), int(n_bg),
+            vp(bg_index_ptr), vp(q0_ptr), vp(dt_ptr), vp(flux_only_ptr or 0), int(n),
+            vp(z_ptr or 0), vp(steps_ptr or 0), vp(lnu_ptr or 0), ctypes.c_uint64(int(seed)),
+            vp(stream_id_ptr or 0), vp(n_accept_ptr or 0),
+            None if record is None else ctypes.byref(record), vp(stream or 0)))
 
     def gen_image(self, params, q, rows, cols, n_real=0, seed=0, install=False):
         """Model image (n_real=0, gen_model) or n_real Poisson realisations of it

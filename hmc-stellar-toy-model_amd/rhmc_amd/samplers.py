@@ -1,7 +1,7 @@
 """The reference's older `samplers` API, routed to the MI355X engine:
 `lightsource_gym` with its three-stage pipeline — `find_peaks` (seed stars),
-`HMC_find_best_dt` (the step vector, default branch) and unit-mass HMC
-(`HMC_random`).
+`HMC_find_best_dt` (the step vector: the default branch and the step-size
+search) and unit-mass HMC (`HMC_random`).
 
 Mirrors jaekor91/HMC-stellar-toy-model `samplers.py` (file:line per method):
 same class name, attributes (set after construction, like the reference's
@@ -9,12 +9,14 @@ scripts: `gym.Nobjs`, `gym.d = 3 * Nobjs`, `gym.dt = <vector [d]>`), method
 names, argument meaning, global-NumPy-RNG draw order and results.
 
 What runs where:
-  * dVdq, V, the HMC_random trajectories and find_peaks' gradient descent
-    of the seeds run in librhmc.so (rhmc_gradient kind 0, rhmc_energy without
-    the position check, rhmc_hmc_random, rhmc_find_peaks).  No CPU fallback.
+  * dVdq, V, the HMC_random trajectories, find_peaks' gradient descent of
+    the seeds and the trials of HMC_find_best_dt's search run in librhmc.so
+    (rhmc_gradient kind 0, rhmc_energy without the position check,
+    rhmc_hmc_random, rhmc_find_peaks, rhmc_dt_trials).  No CPU fallback.
   * E, K, p_sample, the MH bookkeeping, find_peaks' seed grid and its merge of
-    near-duplicate peaks (merge_peaks) stay on the host (NumPy), like the
-    reference.
+    near-duplicate peaks (merge_peaks), and everything between the trials of
+    the search (the coarse ladder, the bisection, the per-star Poisson
+    realisation) stay on the host (NumPy), like the reference.
 
 Quirks kept on purpose (samplers.py:519-552): the flux-wall flip mask is
 never cleared inside a trajectory, and a trajectory whose last step flipped
@@ -22,8 +24,12 @@ is evaluated with the momentum it started from.  HMC_random requires
 Nchain == 1 (assert, like the reference); HMC_random_batched runs many chains
 at once and, with one chain, draws exactly what HMC_random draws.
 
-Not built: HMC_find_best_dt's step-size search (default=False; it needs a
-per-star residual image as the background, the kernels take a constant B).
+HMC_find_best_dt's step-size search (default=False, samplers.py:306-456)
+takes one more keyword than the reference's call: rng="numpy" runs the
+reference draw for draw from the global NumPy stream (one rhmc_dt_trials call
+per trial), rng="philox" searches all stars at once with the device's draws
+(one call per round of trials).  Without rng the call raises
+NotImplementedError, as before the search existed.
 Out of scope: RHMC_random_diag / RHMC_random, the GMM testbed and
 the plots.
 """
@@ -71,6 +77,73 @@ def merge_peaks(q_seed, flux_to_count, dr_tol=1., dmag_tol=0.5):
         if q_seed.shape[0] == 0:
             break
     return np.vstack(final)
+
+
+DT_COARSE_CAP = 64      # trials of one coarse loop before the search gives up
+
+
+def dt_stream_id(star, phase, stage, trial):
+    """The Philox stream of one trial of HMC_find_best_dt(rng="philox"):
+    star << 32 | phase << 31 | stage << 30 | trial, with phase 0 = flux, 1 = xy
+    (samplers.py:317), stage 0 = coarse (:330), 1 = fine (:390), and trial the
+    0-based number of the trial inside its loop (< 2^30)."""
+    assert 0 <= trial < (1 << 30) and 0 <= star < (1 << 32)
+    return (int(star) << 32) | (int(phase) << 31) | (int(stage) << 30) | int(trial)
+
+
+def dt_star_search(star, f0, Niter_per_trial, Ntrial, dt_f_coeff, dt_xy_coeff, A_target_f,
+                   A_target_xy):
+    """samplers.py:309-456 for one star as a generator: everything between
+    the trials, in the reference's NumPy expressions.  Yields (phase, stage,
+    trial number, dt [3]) for the trial to run next and is sent the number of
+    accepted iterations; returns (dt_f, dt_xy)."""
+    dt_xy = dt_xy_coeff / f0
+    dt_f = dt_f_coeff * f0
+    for k in range(2):
+        if k == 0:
+            dt = np.array([dt_f, 0, 0])
+            A_target = A_target_f
+        else:
+            dt = np.array([dt_f, dt_xy, dt_xy])
+            A_target = A_target_xy
+        n_coarse = 0
+        while True:                                           # :330
+            if n_coarse == DT_COARSE_CAP:
+                raise RuntimeError("HMC_find_best_dt: star %d did not reach the target "
+                                   "acceptance in %d coarse trials" % (star, DT_COARSE_CAP))
+            A_rate = (yield k, 0, n_coarse, dt.copy())
+            n_coarse += 1
+            A_rate /= float(Niter_per_trial)                  # :371
+            if A_rate < A_target:                             # :374-378
+                if k == 0:
+                    dt /= 10.
+                else:
+                    dt[1:] = dt[1:] / 10.
+            else:
+                break
+        counter = 0                                           # :383-387
+        dt_left = dt
+        dt_right = 10. * dt
+        if k == 1:
+            dt_right[0] = dt_f
+        while counter < Ntrial:                               # :390
+            counter += 1
+            dt = (dt_left + dt_right) / 2.                    # :394
+            if k == 1:
+                dt[0] = dt_f
+            A_rate = (yield k, 1, counter - 1, dt.copy())
+            A_rate /= float(Niter_per_trial)                  # :438
+            if np.abs(A_rate - A_target) < 1e-2:              # :441-446
+                break
+            elif A_rate > A_target:
+                dt_left = dt
+            else:
+                dt_right = dt
+        if k == 0:                                            # :450-453
+            dt_f = dt[0]
+        else:
+            dt_xy = dt[1] * 10
+    return dt_f, dt_xy
 
 
 class lightsource_gym(object):
@@ -216,10 +289,28 @@ class lightsource_gym(object):
 
     def HMC_find_best_dt(self, q_model_0=None, steps_min=10, steps_max=50, Niter_per_trial=10,
                          Ntrial=10, dt_f_coeff=1., dt_xy_coeff=10., default=False,
-                         A_target_f=0.9, A_target_xy=0.5):
-        """samplers.py:257-303, the default=True branch: Nobjs, d and the step
-        vector dt = (dt_f_coeff f, dt_xy_coeff / f, dt_xy_coeff / f) per star.
-        The search (default=False, :306-456) is not built."""
+                         A_target_f=0.9, A_target_xy=0.5, rng=None, grad="reference", seed=0):
+        """samplers.py:257-456: Nobjs, d and the step vector dt.  default=True:
+        dt = (dt_f_coeff f, dt_xy_coeff / f, dt_xy_coeff / f) per star (:295-303).
+        default=False is the step-size search (:306-456), its trials on the GPU
+        (rhmc_dt_trials) and `rng` (which the reference's call does not have)
+        saying where the draws come from:
+          rng="numpy"   the reference draw for draw from the global NumPy
+                        stream: per star the Poisson realisation, per trial
+                        randn(3), randint(steps_min, steps_max, 1), random(1)
+                        for each iteration, then one call with one task;
+          rng="philox"  all stars at once: the Nobjs realisations first, in star
+                        order, from the global stream; then every star walks its
+                        own coarse / fine search and each round is one call over
+                        the stars that still have a trial to run, with the
+                        device's Philox draws under `seed` and the stream
+                        dt_stream_id(star, phase, stage, trial);
+          rng=None      NotImplementedError.
+        grad="reference" uses the flux gradient for all three coordinates, as
+        the reference's call does (dVdq_single's default f_only=True),
+        grad="full" the true gradient.  A coarse loop that has not reached its
+        target after 64 trials raises RuntimeError naming the star (the
+        reference would loop forever, e.g. when V(q0) is NaN)."""
         if q_model_0 is None:
             print("Use found seeds for inference.")
             q_model_0 = self.q_seed
@@ -227,16 +318,96 @@ class lightsource_gym(object):
         self.Nobjs = q_model_0.shape[0]
         self.d = self.Nobjs * 3
         self.dt = np.zeros(self.d)
-        if not default:
+        if default:
+            for i in range(self.Nobjs):
+                f0, x0, y0 = q_model_0[i]
+                dt_xy = dt_xy_coeff / f0
+                dt_f = dt_f_coeff * f0
+                self.dt[3 * i:3 * i + 3] = np.array([dt_f, dt_xy, dt_xy])
+            return
+        if rng is None:
             raise NotImplementedError(
                 "HMC_find_best_dt(default=False): the step-size search perturbs one star "
                 "against the residual image of the others as its background, and the "
-                "kernels take a constant background B; use default=True")
-        for i in range(self.Nobjs):
-            f0, x0, y0 = q_model_0[i]
-            dt_xy = dt_xy_coeff / f0
-            dt_f = dt_f_coeff * f0
-            self.dt[3 * i:3 * i + 3] = np.array([dt_f, dt_xy, dt_xy])
+                "kernels take a constant background B; use default=True, or name the "
+                "source of the search's draws: rng=\"numpy\" (the reference's stream) or "
+                "rng=\"philox\" (all stars at once, rhmc_dt_trials)")
+        if rng not in ("numpy", "philox"):
+            raise ValueError("rng must be None, \"numpy\" or \"philox\"")
+        kw = dict(steps_min=steps_min, steps_max=steps_max, Niter_per_trial=Niter_per_trial,
+                  Ntrial=Ntrial, dt_f_coeff=dt_f_coeff, dt_xy_coeff=dt_xy_coeff,
+                  A_target_f=A_target_f, A_target_xy=A_target_xy, grad=grad)
+        if rng == "numpy":
+            for l in range(self.Nobjs):
+                bg = self._dt_background(q_model_0, l)
+                self.dt[3 * l:3 * l + 3] = self._dt_search_numpy(q_model_0[l], l, bg, **kw)
+            return
+        bgs = np.stack([self._dt_background(q_model_0, l) for l in range(self.Nobjs)])
+        res = self.dt_search_philox(q_model_0, bgs, range(self.Nobjs), seed=seed, **kw)
+        for l in range(self.Nobjs):
+            self.dt[3 * l:3 * l + 3] = res[l]
+
+    def _dt_background(self, q_model_0, l):
+        """samplers.py:314-315: a Poisson realisation of the model of all the
+        stars (global NumPy stream) minus star l."""
+        f0, x0, y0 = q_model_0[l]
+        model_data = self.gen_mock_data(q_model_0, return_data=True)
+        model_data -= f0 * gauss_PSF(self.num_rows, self.num_cols, x0, y0,
+                                     FWHM=self.PSF_FWHM_pix)
+        return model_data
+
+    def _dt_search_numpy(self, q0, l, bg, steps_min, steps_max, Niter_per_trial, Ntrial,
+                         dt_f_coeff, dt_xy_coeff, A_target_f, A_target_xy, grad):
+        ctx, P = self._context(), self._params()
+        opts = capi.make_dt_opts(Niter_per_trial, grad, steps_min, steps_max)
+        gen = dt_star_search(l, q0[0], Niter_per_trial, Ntrial, dt_f_coeff, dt_xy_coeff,
+                             A_target_f, A_target_xy)
+        n = Niter_per_trial
+        z, steps, lnu = np.zeros((n, 3)), np.zeros(n, np.int32), np.zeros(n)
+        req = next(gen)
+        while True:
+            k, _, _, dt = req
+            for i in range(n):                                # :343, :351, :365
+                z[i] = np.random.randn(3)
+                steps[i] = np.random.randint(low=steps_min, high=steps_max, size=1)[0]
+                lnu[i] = np.log(np.random.random(1))[0]
+            n_acc = ctx.dt_trials(P, opts, bg, [0], q0, dt, flux_only=[k == 0], z=z,
+                                  steps=steps, lnu=lnu)
+            try:
+                req = gen.send(int(n_acc[0]))
+            except StopIteration as e:
+                dt_f, dt_xy = e.value
+                return np.array([dt_f, dt_xy, dt_xy])         # :456
+
+    def dt_search_philox(self, q_model_0, bgs, stars, steps_min=10, steps_max=50,
+                         Niter_per_trial=10, Ntrial=10, dt_f_coeff=1., dt_xy_coeff=10.,
+                         A_target_f=0.9, A_target_xy=0.5, grad="reference", seed=0):
+        """The search of HMC_find_best_dt(rng="philox") for the stars `stars`
+        of q_model_0 against their backgrounds bgs[star]: {star: step vector
+        [3]}.  A star's result does not depend on which other stars are
+        searched with it."""
+        q_model_0 = np.asarray(q_model_0, dtype=float).reshape(-1, 3)
+        ctx, P = self._context(), self._params()
+        opts = capi.make_dt_opts(Niter_per_trial, grad, steps_min, steps_max)
+        gens, req, out = {}, {}, {}
+        for l in stars:
+            gens[l] = dt_star_search(l, q_model_0[l, 0], Niter_per_trial, Ntrial, dt_f_coeff,
+                                     dt_xy_coeff, A_target_f, A_target_xy)
+            req[l] = next(gens[l])
+        while req:
+            act = sorted(req)
+            n_acc = ctx.dt_trials(
+                P, opts, bgs, act, q_model_0[act], [req[l][3] for l in act],
+                flux_only=[req[l][0] == 0 for l in act], seed=seed,
+                stream_id=[dt_stream_id(l, *req[l][:3]) for l in act])
+            for l, a in zip(act, n_acc):
+                try:
+                    req[l] = gens[l].send(int(a))
+                except StopIteration as e:
+                    del req[l]
+                    dt_f, dt_xy = e.value
+                    out[l] = np.array([dt_f, dt_xy, dt_xy])
+        return out
 
     # ------------------------------------------------------------- sampling
     def _trajectories(self, q, p, steps):

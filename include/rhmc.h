@@ -51,6 +51,11 @@
  *       seeds (samplers.py:190-221) on V_single / dVdq_single (:77-127)
  *       against the pure-background model; the seed grid (:157-180) and the
  *       merge of near-duplicates (:232-252) stay on the host.
+ *   rhmc_dt_trials / rhmc_dt_trials_device
+ *       the trial of samplers.lightsource_gym.HMC_find_best_dt's step-size
+ *       search (samplers.py:332-371): Metropolis iterations of explicit
+ *       leapfrog on one star against a background image; the coarse / fine
+ *       search around the trials (:327-456) stays on the host.
  *   rhmc_params
  *       the instance attributes the step reads: dt, g_xx,
  *       g_ff, g_ff2, g0, g1, g2, B_count, f_lim, mB (-> f_low),
@@ -197,13 +202,16 @@ typedef struct rhmc_ctx rhmc_ctx;
  *   descent kernel where it exists (32/48/64-px images, a PSF narrow enough
  *   for the 28-px window, no forced per-wave family), 0 = always the stepwise
  *   path (gradient / update / energy / update launches per step).
+ * RHMC_OPT_DT_LANES: lanes per task of rhmc_dt_trials, 0 (default) = the
+ *   library's choice (256), 64 or 256 (the A/B of DESIGN.md section 4e).
  */
 enum {
   RHMC_OPT_KERNEL = 1,
   RHMC_OPT_MH_FUSED = 2,
   RHMC_OPT_WINDOW_SPLIT = 3,
   RHMC_OPT_TABLES = 4,
-  RHMC_OPT_PEAKS_FUSED = 5
+  RHMC_OPT_PEAKS_FUSED = 5,
+  RHMC_OPT_DT_LANES = 6
 };
 enum {
   RHMC_TABLES_STREAM = 0,
@@ -469,6 +477,79 @@ int rhmc_find_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* 
 int rhmc_find_peaks_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* opts,
                            double* d_q, int64_t n, int32_t* d_steps, int32_t* d_status,
                            double* d_V, void* stream);
+
+/*
+ * The trial of samplers.lightsource_gym.HMC_find_best_dt's step-size search
+ * (samplers.py:332-371, identical at :399-438), n independent tasks.  Task t
+ * starts at q0[t] = (f, x, y) with the step vector dt[t] against the
+ * background image bg[bg_index[t]] (fp64, the context's image shape) and the
+ * context's data image D, and runs opts->n_iter iterations i of
+ *   p  = z[t][i]                    (flux_only[t] != 0: p[1] = p[2] = 0, :343-345)
+ *   E0 = V(q) + (p.p)/2             V = -sum(D ln L - L), L = bg + f PSF(x, y)
+ *                                   over all pixels (:121-127)
+ *   ph = p - dt G(q)/2              (:352)
+ *   steps[t][i] times: q = q + dt ph ; ph = ph - dt G(q)      (:354-356)
+ *   p  = ph + dt G(q)/2 ; dE = V(q) + (p.p)/2 - E0
+ *   accept when dE < 0 or lnu[t][i] < -dE (:366), else q returns to the
+ *   iteration's start.
+ * n_accept[t] counts the accepted iterations.  PSF and pixel convention as at
+ * rhmc_gen_image.  opts->grad selects G: RHMC_DT_GRAD_REFERENCE is what the
+ * reference's call computes, dVdq_single with its default f_only=True (:77,
+ * :102-104): the flux gradient -sum (D/L - 1) PSF used for all three
+ * coordinates; RHMC_DT_GRAD_FULL is the true (dV/df, dV/dx, dV/dy) (:93-101).
+ * There is no flux wall and no confinement; non-finite values propagate
+ * (0 * NaN stays NaN, so dt = (dt_f, 0, 0) with flux_only needs no mode of its
+ * own) and end in a rejection.  A task's result depends on nothing but its own
+ * inputs (not on n, its position or its batch-mates).
+ *
+ * Draws: z [n][n_iter][3] standard normals, steps [n][n_iter] and lnu
+ * [n][n_iter] = log(u) from the host (the reference's randn(3), randint(
+ * steps_min, steps_max, 1), log(random(1)) per iteration), all three or none.
+ * With none the device draws them with Philox-4x32-10 under key `seed`, counter
+ * (draw, iteration, stream_id[t]): draws 0 and 1 are the Box-Muller pairs of z,
+ * 0x80000001 the step count, uniform on [steps_min, steps_max), 0x80000000 u in
+ * (0, 1]; a task's draws depend on nothing but seed and stream_id[t].
+ * stream_id is read only then; steps_min / steps_max likewise (0 <= steps_min
+ * < steps_max <= 65536).
+ *
+ * rec (nullable, every member nullable): per iteration dE, accept, q after
+ * the iteration, and the draws used (z as drawn, before flux_only zeroes it).
+ * Only P->B_count and P->fwhm_pix are read from P (B_count not by the trial).
+ * n = 0 is a no-op.  RHMC_ERR_ARG: NULL ctx, P, opts, bg, bg_index, q0 or dt
+ * (stream_id without host draws), n < 0, n_bg < 1, n_iter outside 1..1024, an
+ * unknown grad, non-zero reserved, only some of z / steps / lnu, and on the
+ * host entry point bg_index outside [0, n_bg) or steps outside 0..65535 (the
+ * device entry point clamps both into range instead).
+ */
+enum { RHMC_DT_GRAD_REFERENCE = 0, RHMC_DT_GRAD_FULL = 1 };
+typedef struct rhmc_dt_opts {
+  int32_t n_iter;      /* HMC_find_best_dt's Niter_per_trial, 1..1024          */
+  int32_t grad;        /* RHMC_DT_GRAD_*                                       */
+  int32_t steps_min;   /* device draws: steps uniform on [steps_min, steps_max) */
+  int32_t steps_max;
+  int32_t reserved[2]; /* must be 0                                            */
+} rhmc_dt_opts;
+typedef struct rhmc_dt_record {
+  double* dE;          /* [n][n_iter]                                          */
+  int32_t* accept;     /* [n][n_iter]                                          */
+  double* q;           /* [n][n_iter][3] q after the iteration                 */
+  double* z;           /* [n][n_iter][3] the draws used                        */
+  int32_t* steps;      /* [n][n_iter]                                          */
+  double* lnu;         /* [n][n_iter]                                          */
+} rhmc_dt_record;
+int rhmc_dt_trials(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opts* opts,
+                   const double* bg, int32_t n_bg, const int32_t* bg_index, const double* q0,
+                   const double* dt, const int32_t* flux_only, int64_t n, const double* z,
+                   const int32_t* steps, const double* lnu, uint64_t seed,
+                   const uint64_t* stream_id, int32_t* n_accept, const rhmc_dt_record* rec);
+/* Device pointers (rec itself is a host struct of device pointers),
+ * asynchronous on `stream`. */
+int rhmc_dt_trials_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opts* opts,
+                          const double* d_bg, int32_t n_bg, const int32_t* d_bg_index,
+                          const double* d_q0, const double* d_dt, const int32_t* d_flux_only,
+                          int64_t n, const double* d_z, const int32_t* d_steps,
+                          const double* d_lnu, uint64_t seed, const uint64_t* d_stream_id,
+                          int32_t* d_n_accept, const rhmc_dt_record* rec, void* stream);
 
 #ifdef __cplusplus
 }

@@ -146,6 +146,42 @@ int check_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts* o, c
   return RHMC_OK;
 }
 
+// The checks the two diag_random entry points share (n == 0 after them: a
+// no-op), arguments before the context like check_peaks.  host_call: steps
+// is readable, so every length and the trace's row count are checked (the
+// kernels of the device entry point write no row past trace_rows).
+int check_diag(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* o, const double* q,
+               const double* p, const int32_t* steps, int64_t n, int32_t K, const double* trace,
+               bool host_call) {
+  if (!P) return fail(RHMC_ERR_ARG, "params is NULL");
+  if (!o) return fail(RHMC_ERR_ARG, "opts is NULL");
+  if (n < 0) return fail(RHMC_ERR_ARG, "n_chains < 0");
+  if (n > ((int64_t)1 << 40)) return fail(RHMC_ERR_ARG, "n_chains too large");
+  if (K < 1 || K > kMaxK) return fail(RHMC_ERR_ARG, "K must be in [1, 1024]");
+  if (o->reserved != 0) return fail(RHMC_ERR_ARG, "opts.reserved must be 0");
+  if (!std::isfinite(o->dt)) return fail(RHMC_ERR_ARG, "opts.dt is not finite");
+  if (!(std::isfinite(o->factor1) && o->factor1 > 0.0))
+    return fail(RHMC_ERR_ARG, "opts.factor1 must be finite and > 0");
+  if (!steps) return fail(RHMC_ERR_ARG, "steps is NULL");
+  if (n > 0 && (!q || !p)) return fail(RHMC_ERR_ARG, "q/p is NULL");
+  if (trace && o->trace_rows < 2)
+    return fail(RHMC_ERR_ARG, "opts.trace_rows must exceed the longest trajectory (>= 2)");
+  if (host_call) {
+    int32_t longest = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      if (steps[i] < 1) return fail(RHMC_ERR_ARG, "steps[i] must be >= 1");
+      longest = steps[i] > longest ? steps[i] : longest;
+    }
+    if (trace && o->trace_rows <= longest)
+      return fail(RHMC_ERR_ARG, "opts.trace_rows = " + std::to_string(o->trace_rows) +
+                                    " must exceed the longest trajectory (" +
+                                    std::to_string(longest) + " steps)");
+  }
+  if (!ctx) return fail(RHMC_ERR_ARG, "ctx is NULL");
+  if (n > 0 && !ctx->d_D) return fail(RHMC_ERR_ARG, "no image uploaded");
+  return RHMC_OK;
+}
+
 // The checks the two dt_trials entry points share (n == 0 after them: a
 // no-op), arguments before the context like check_peaks.
 int check_dt(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opts* o, const double* bg,
@@ -722,6 +758,35 @@ int rhmc_hmc_random(rhmc_ctx* ctx, const rhmc_params* P, const double* dt, doubl
   return st.run([&] {
     return launch_hmc_random(ctx, P, st.dev<double>(id), st.dev<double>(iq), st.dev<double>(ip),
                              st.dev<int32_t>(in), n_chains, K, st.dev<int32_t>(is), ctx->stream);
+  });
+}
+
+int rhmc_diag_random_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* opts,
+                            double* d_q, double* d_p, const int32_t* d_steps, int64_t n_chains,
+                            int32_t K, int32_t* d_status, double* d_trace, void* stream) {
+  if (int rc = check_diag(ctx, P, opts, d_q, d_p, d_steps, n_chains, K, d_trace, false)) return rc;
+  if (n_chains == 0) return RHMC_OK;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  return launch_diag_random(ctx, P, opts, d_q, d_p, d_steps, n_chains, K, d_status, d_trace, s);
+}
+
+int rhmc_diag_random(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* opts, double* q,
+                     double* p, const int32_t* steps, int64_t n_chains, int32_t K,
+                     int32_t* status, double* trace) {
+  if (int rc = check_diag(ctx, P, opts, q, p, steps, n_chains, K, trace, true)) return rc;
+  if (n_chains == 0) return RHMC_OK;
+  const size_t sb = (size_t)n_chains * 3 * K * sizeof(double);
+  const size_t tb = (size_t)n_chains * sizeof(int32_t);
+  HIP_TRY(hipSetDevice(ctx->device));
+  Staging st(ctx);  // rows past a chain's trajectory come back as they went in
+  const int iq = st.add(q, sb, Staging::kInOut), ip = st.add(p, sb, Staging::kInOut);
+  const int is = st.add(status, status ? tb : 0, Staging::kOut);
+  const int in = st.add(steps, tb, Staging::kIn);
+  const int it = st.add(trace, trace ? sb * (size_t)opts->trace_rows : 0, Staging::kInOut);
+  return st.run([&] {
+    return launch_diag_random(ctx, P, opts, st.dev<double>(iq), st.dev<double>(ip),
+                              st.dev<int32_t>(in), n_chains, K, st.dev<int32_t>(is),
+                              st.dev<double>(it), ctx->stream);
   });
 }
 

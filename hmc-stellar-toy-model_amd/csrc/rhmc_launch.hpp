@@ -1006,14 +1006,14 @@ int launch_integrate(rhmc_ctx* ctx, const rhmc_params* P, int32_t solver, double
   }
 }
 
-int launch_hmc_random(rhmc_ctx* ctx, const rhmc_params* P, const double* d_dt, double* d_q,
-                      double* d_p, const int32_t* d_steps, int64_t n, int32_t K, int32_t* d_st,
-                      hipStream_t s) {
-  Consts c;
-  int rc = make_consts(P, &c);
-  if (rc) return rc;
-  if (n == 0) return RHMC_OK;
-  if (!d_dt || !d_steps) return fail(RHMC_ERR_ARG, "dt/steps is NULL");
+// HMC_random's trajectories, or with `dg` (device pointers in it)
+// RHMC_random_diag's: the same plan and launch shapes, the kernels' DIAG
+// bodies, d_dt unused.
+template <bool DIAG>
+int launch_hmc_random_t(rhmc_ctx* ctx, const Consts& c, const double* d_dt, double* d_q,
+                        double* d_p, const int32_t* d_steps, int64_t n, int32_t K, int32_t* d_st,
+                        hipStream_t s, const DiagArgs& dg) {
+  int rc;
   Plan pl;
   if ((rc = plan_for(ctx, c, Op::HmcRandom, K, n, &pl))) return rc;
   switch (pl.family) {
@@ -1024,15 +1024,20 @@ int launch_hmc_random(rhmc_ctx* ctx, const rhmc_params* P, const double* d_dt, d
       return launch_k1_w28(ctx, pl.f32, n,
                            [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
         using DT = typename decltype(dt)::type;
-        hipLaunchKernelGGL((hmc_random_k1_tiledr<decltype(img)::value, DT>), grid, block, lds, s,
-                           t, d_dt, d_steps);
+        if constexpr (DIAG)
+          hipLaunchKernelGGL((diag_hmc_random_k1_tiledr<decltype(img)::value, DT>), grid, block,
+                             lds, s, t, d_steps, dg);
+        else
+          hipLaunchKernelGGL((hmc_random_k1_tiledr<decltype(img)::value, DT>), grid, block, lds,
+                             s, t, d_dt, d_steps);
       });
     }
     case Family::PixMajor:
     case Family::MultiWin: {
-      const LeapArgsKR t = kr_args(ctx, c, d_q, d_p, nullptr, d_st, n, K, 0, d_dt, d_steps);
+      LeapArgsKR t = kr_args(ctx, c, d_q, d_p, nullptr, d_st, n, K, 0, d_dt, d_steps);
+      t.diag = dg;
       HIP_TRY(hipSetDevice(ctx->device));
-      return launch_multi<kSolverHmcRandom>(ctx, pl, t, 0, s);
+      return launch_multi<DIAG ? kSolverDiagRandom : kSolverHmcRandom>(ctx, pl, t, 0, s);
     }
     default: {  // slotted (hmc_random_win_kernel)
       LeapArgs a = leap_args(ctx, c, d_q, d_p, nullptr, d_st, n, K, 0);
@@ -1040,12 +1045,43 @@ int launch_hmc_random(rhmc_ctx* ctx, const rhmc_params* P, const double* d_dt, d
       if ((rc = slotted_shape(ctx, pl, K, n, s, true, &a.g, &sh))) return rc;
       return with_path(pl.path, K, [&](auto gt, auto st) {
         using G = typename decltype(gt)::type;
-        hipLaunchKernelGGL((hmc_random_win_kernel<G, decltype(st)::value>), sh.grid, sh.block,
-                           sh.lds, s, a, d_dt, d_steps);
+        if constexpr (DIAG)
+          hipLaunchKernelGGL((diag_hmc_random_win_kernel<G, decltype(st)::value>), sh.grid,
+                             sh.block, sh.lds, s, a, d_steps, dg);
+        else
+          hipLaunchKernelGGL((hmc_random_win_kernel<G, decltype(st)::value>), sh.grid, sh.block,
+                             sh.lds, s, a, d_dt, d_steps);
         return launch_status();
       });
     }
   }
+}
+
+int launch_hmc_random(rhmc_ctx* ctx, const rhmc_params* P, const double* d_dt, double* d_q,
+                      double* d_p, const int32_t* d_steps, int64_t n, int32_t K, int32_t* d_st,
+                      hipStream_t s) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  if (n == 0) return RHMC_OK;
+  if (!d_dt || !d_steps) return fail(RHMC_ERR_ARG, "dt/steps is NULL");
+  return launch_hmc_random_t<false>(ctx, c, d_dt, d_q, d_p, d_steps, n, K, d_st, s, DiagArgs{});
+}
+
+// RHMC_random_diag's trajectories (rhmc_diag_random; check_diag has passed).
+// d_trace: nullable [n][o->trace_rows][3K].
+int launch_diag_random(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* o, double* d_q,
+                       double* d_p, const int32_t* d_steps, int64_t n, int32_t K, int32_t* d_st,
+                       double* d_trace, hipStream_t s) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  DiagArgs dg;
+  dg.dt = o->dt;
+  dg.inv_f1 = 1.0 / o->factor1;
+  dg.trace = d_trace;
+  dg.rows = d_trace ? o->trace_rows : 0;
+  return launch_hmc_random_t<true>(ctx, c, nullptr, d_q, d_p, d_steps, n, K, d_st, s, dg);
 }
 
 // ---------------------------------------------------------------------------

@@ -799,11 +799,16 @@ __global__ void __launch_bounds__(256) integrate_win_kernel(LeapArgs a, int f_po
 // last step flipped, p_tmp keeps the momentum the trajectory started from
 // (:547-550 update p_half, not p_tmp) — status bit RHMC_STATUS_REFLECT_F
 // marks those chains.  One wave per chain, star 64 s + lane in slot s.
-template <class G, int SLOTS>
-__global__ void __launch_bounds__(256) hmc_random_win_kernel(LeapArgs a,
-                                                             const double* __restrict__ dtv,
-                                                             const int32_t* __restrict__ steps) {
-  extern __shared__ double lds[];
+// DIAG: RHMC_random_diag's trajectory instead (samplers.py:766-800; dtv
+// unused): the one step dg.dt, the drift divided by the mass matrix at the
+// flux before it, dlnDetdq + dpMpdq in the flux force (diag_force_f, with the
+// start momentum, which s.pf, s.px, s.py keep for the REFLECT_F return
+// anyway), the same wall quirks, and q after every step to dg.trace.
+template <class G, int SLOTS, bool DIAG>
+__device__ __forceinline__ void hmc_random_win_body(double* lds, const LeapArgs& a,
+                                                    const double* __restrict__ dtv,
+                                                    const int32_t* __restrict__ steps,
+                                                    const DiagArgs& dg) {
   const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g.rows, a.g.cols, a.g.work);
   const Consts& c = a.c;
   const int W = blockDim.x / kWave;
@@ -817,13 +822,40 @@ __global__ void __launch_bounds__(256) hmc_random_win_kernel(LeapArgs a,
   double dtf[SLOTS], dtx[SLOTS], dty[SLOTS];
 #pragma unroll
   for (int t = 0; t < SLOTS; ++t) {
-    const int ks = s.own[t] ? kWave * t + lane : 0;
-    dtf[t] = dtv[3 * ks];
-    dtx[t] = dtv[3 * ks + 1];
-    dty[t] = dtv[3 * ks + 2];
+    if constexpr (DIAG) {
+      dtf[t] = dtx[t] = dty[t] = dg.dt;
+    } else {
+      const int ks = s.own[t] ? kWave * t + lane : 0;
+      dtf[t] = dtv[3 * ks];
+      dtx[t] = dtv[3 * ks + 1];
+      dty[t] = dtv[3 * ks + 2];
+    }
   }
   double gf[SLOTS], gx[SLOTS], gy[SLOTS];
+  auto force = [&]() {  // DIAG: dVdq + dlnDetdq + dpMpdq (:766)
+    if constexpr (DIAG) {
+#pragma unroll
+      for (int t = 0; t < SLOTS; ++t)
+        gf[t] = diag_force_f(gf[t], s.f[t], s.pf[t] * s.pf[t],
+                             s.px[t] * s.px[t] + s.py[t] * s.py[t], dg.inv_f1);
+    }
+  };
+  auto trace = [&](int row) {  // DIAG: q to row `row` of the chain's trace
+    if constexpr (DIAG) {
+      if (!dg.trace || row >= dg.rows) return;
+#pragma unroll
+      for (int t = 0; t < SLOTS; ++t) {
+        if (!s.own[t]) continue;
+        double* r = dg.trace + (chain * dg.rows + row) * 3 * K + 3 * (kWave * t + lane);
+        r[0] = s.f[t];
+        r[1] = s.x[t];
+        r[2] = s.y[t];
+      }
+    }
+  };
+  trace(0);
   G::template gradient<SLOTS>(gctx, K, s.f, s.x, s.y, c, lc, false, gf, gx, gy);
+  force();
   double hf[SLOTS], hx[SLOTS], hy[SLOTS];
   bool iflip[SLOTS];
 #pragma unroll
@@ -839,15 +871,21 @@ __global__ void __launch_bounds__(256) hmc_random_win_kernel(LeapArgs a,
     bool below_any = false;
 #pragma unroll
     for (int t = 0; t < SLOTS; ++t) {
-      s.f[t] = s.f[t] + dtf[t] * hf[t];                                 // :523
-      s.x[t] = s.x[t] + dtx[t] * hx[t];
-      s.y[t] = s.y[t] + dty[t] * hy[t];
+      if constexpr (DIAG) {                                             // :770-771
+        diag_drift(s.f[t], s.x[t], s.y[t], hf[t], hx[t], hy[t], dg.dt, dg.inv_f1);
+      } else {
+        s.f[t] = s.f[t] + dtf[t] * hf[t];                               // :523
+        s.x[t] = s.x[t] + dtx[t] * hx[t];
+        s.y[t] = s.y[t] + dty[t] * hy[t];
+      }
       const bool below = s.own[t] && s.f[t] < c.f_lim;                  // :526-529
       iflip[t] = iflip[t] || below;
       below_any = below_any || below;
     }
     flip = __builtin_amdgcn_ballot_w64(below_any) != 0;
+    trace(i + 1);
     G::template gradient<SLOTS>(gctx, K, s.f, s.x, s.y, c, lc, false, gf, gx, gy);
+    force();
 #pragma unroll
     for (int t = 0; t < SLOTS; ++t) {
       const double kept = -hf[t];                                       // :531
@@ -869,6 +907,22 @@ __global__ void __launch_bounds__(256) hmc_random_win_kernel(LeapArgs a,
     }
   }
   win_store<SLOTS>(a, chain, chain, 3 * (int64_t)K, K, s, 0, 0, st);
+}
+
+template <class G, int SLOTS>
+__global__ void __launch_bounds__(256) hmc_random_win_kernel(LeapArgs a,
+                                                             const double* __restrict__ dtv,
+                                                             const int32_t* __restrict__ steps) {
+  extern __shared__ double lds[];
+  hmc_random_win_body<G, SLOTS, false>(lds, a, dtv, steps, DiagArgs{});
+}
+
+// The DIAG body (rhmc_diag_random).
+template <class G, int SLOTS>
+__global__ void __launch_bounds__(256) diag_hmc_random_win_kernel(
+    LeapArgs a, const int32_t* __restrict__ steps, DiagArgs dg) {
+  extern __shared__ double lds[];
+  hmc_random_win_body<G, SLOTS, true>(lds, a, nullptr, steps, dg);
 }
 
 // Star 64 t + lane's (f, x, y) of a chain (lanes without a star: star 0's).

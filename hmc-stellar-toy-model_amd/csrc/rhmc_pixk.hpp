@@ -359,7 +359,7 @@ struct PixK {
 
 // Two chains per wave, W waves per workgroup, one star per lane (K <= KMAX).
 // SOLVER as in leapfrog_kr: RHMC_single_step, an explicit integrator (f_pos =
-// the flux wall) or kSolverHmcRandom.  Ragged sets (a.Kc): each chain's own
+// the flux wall), kSolverHmcRandom or kSolverDiagRandom.  Ragged sets (a.Kc): each chain's own
 // row and star count; the two chains of a wave may differ in K — everything
 // that depends on it is per lane (a chain's lanes), and the pixel passes run
 // all KMAX slots with zero tables for the stars a chain lacks — so a chain's
@@ -421,9 +421,14 @@ leapfrog_pk(LeapArgsKR a, int f_pos) {
   if constexpr (SOLVER == RHMC_SOLVER_IMPLICIT) {
     km_steps<1, decltype(grad), true>(f, x, y, pf, px, py, own, tab, a.n_steps,
                                       (double)(IMG - 1), c, lc, grad, it_p, it_q, st);
-  } else if constexpr (SOLVER == kSolverHmcRandom) {
-    if (km_hmc_random_steps<1, decltype(grad), true>(f, x, y, pf, px, py, own, tab,
-                                                     a.steps[chain_r], a.dtv, c, grad)) {
+  } else if constexpr (SOLVER == kSolverHmcRandom || SOLVER == kSolverDiagRandom) {
+    constexpr bool DG = SOLVER == kSolverDiagRandom;
+    double* tr = nullptr;  // the chain's trace rows (a mirrored tail chain writes none)
+    if constexpr (DG)
+      if (a.diag.trace && real) tr = a.diag.trace + chain * a.diag.rows * 3 * K;
+    if (km_hmc_random_steps<1, decltype(grad), true, DG>(f, x, y, pf, px, py, own, tab,
+                                                         a.steps[chain_r], a.dtv, c, grad,
+                                                         a.diag, tr, K, a.p + cbase)) {
       st |= RHMC_STATUS_REFLECT_F;  // p_tmp stays the starting momentum (:547-550)
       pf[0] = own[0] ? a.p[e] : 0.0;
       px[0] = own[0] ? a.p[e + 1] : 0.0;

@@ -611,12 +611,17 @@ integrate_k1_tiledr(LeapArgsK1 a, int f_pos) {
 // at c.f_lim with the reference's quirks (hmc_random_win_kernel: the flip mask
 // is never cleared; a trajectory whose last step flipped keeps its starting
 // momentum, status RHMC_STATUS_REFLECT_F).  dVdq without the metric (:365-425).
-template <int IMG, typename DT>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
-hmc_random_k1_tiledr(LeapArgsK1 a, const double* __restrict__ dtv,
-                     const int32_t* __restrict__ steps) {
+// DIAG: RHMC_random_diag's trajectory instead (samplers.py:766-800; dtv
+// unused): the one step dg.dt, the drift divided by the mass matrix at the
+// flux before it, dlnDetdq + dpMpdq in the flux force (diag_force_f, with the
+// start momentum, which pf, px, py keep for the REFLECT_F return anyway), the
+// same wall quirks, and q after every step to dg.trace when asked for.
+template <int IMG, typename DT, bool DIAG>
+__device__ __forceinline__ void hmc_random_k1_body(double* lds, const LeapArgsK1& a,
+                                                   const double* __restrict__ dtv,
+                                                   const int32_t* __restrict__ steps,
+                                                   const DiagArgs& dg) {
   using TL = TiledR<IMG, 28, DT>;
-  extern __shared__ double lds[];
   DT* simg = reinterpret_cast<DT*>(lds + kExpTab);
   const DT* gimg;
   if constexpr (sizeof(DT) == sizeof(float)) gimg = reinterpret_cast<const DT*>(a.Df);
@@ -638,7 +643,12 @@ hmc_random_k1_tiledr(LeapArgsK1 a, const double* __restrict__ dtv,
   const int64_t base = cr * 3;
   double f = a.q[base], x = a.q[base + 1], y = a.q[base + 2];
   double pf = a.p[base], px = a.p[base + 1], py = a.p[base + 2];
-  const double dtf = dtv[0], dtx = dtv[1], dty = dtv[2];
+  double dtf, dtx, dty;
+  if constexpr (DIAG) {
+    dtf = dtx = dty = dg.dt;
+  } else {
+    dtf = dtv[0], dtx = dtv[1], dty = dtv[2];
+  }
   const LeanConsts lc = lean_consts(c);
   typename TL::Cache cache;
   TL::init(cache);
@@ -646,16 +656,34 @@ hmc_random_k1_tiledr(LeapArgsK1 a, const double* __restrict__ dtv,
   auto grad = [&]() {                              // dVdq (:365-425)
     TL::gradient(lds, simg, cache, f, x, y, c, lc, gf, gx, gy);
     if (c.use_prior) gf += c.alpha / f;            // :408-409
+    if constexpr (DIAG) gf = diag_force_f(gf, f, pf * pf, px * px + py * py, dg.inv_f1);
   };
+  // DIAG: row t of the chain's trace, written by the chain's first lane
+  auto trace = [&](int t) {
+    if constexpr (DIAG) {
+      if (dg.trace && (lane % TL::LPC) == 0 && real && t < dg.rows) {
+        double* r = dg.trace + (chain * dg.rows + t) * 3;
+        r[0] = f;
+        r[1] = x;
+        r[2] = y;
+      }
+    }
+  };
+  trace(0);
   grad();
   double hf = pf - dtf * gf / 2.0, hx = px - dtx * gx / 2.0,  // :519
          hy = py - dty * gy / 2.0;
   bool iflip = false, flip = false;
   const int n = steps[cr];
   for (int t = 0; t < n; ++t) {
-    f = f + dtf * hf;                                          // :523
-    x = x + dtx * hx;
-    y = y + dty * hy;
+    if constexpr (DIAG) {
+      diag_drift(f, x, y, hf, hx, hy, dtf, dg.inv_f1);         // :770-771
+      trace(t + 1);
+    } else {
+      f = f + dtf * hf;                                        // :523
+      x = x + dtx * hx;
+      y = y + dty * hy;
+    }
     flip = f < c.f_lim;                                        // :526-529 (one star)
     iflip = iflip || flip;
     grad();
@@ -685,6 +713,22 @@ hmc_random_k1_tiledr(LeapArgsK1 a, const double* __restrict__ dtv,
     a.p[base + 2] = py;
     if (a.status) a.status[chain] = (int32_t)st;
   }
+}
+
+template <int IMG, typename DT>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
+hmc_random_k1_tiledr(LeapArgsK1 a, const double* __restrict__ dtv,
+                     const int32_t* __restrict__ steps) {
+  extern __shared__ double lds[];
+  hmc_random_k1_body<IMG, DT, false>(lds, a, dtv, steps, DiagArgs{});
+}
+
+// The DIAG body (rhmc_diag_random).
+template <int IMG, typename DT>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
+diag_hmc_random_k1_tiledr(LeapArgsK1 a, const int32_t* __restrict__ steps, DiagArgs dg) {
+  extern __shared__ double lds[];
+  hmc_random_k1_body<IMG, DT, true>(lds, a, nullptr, steps, dg);
 }
 
 }  // namespace rhmc

@@ -56,11 +56,14 @@ struct LeapArgsKR {
   const int32_t* Kc = nullptr;
   const int64_t* rows = nullptr;
   int64_t ld = 0;
+  DiagArgs diag;          // kSolverDiagRandom: step, 1/factor1, trace
 };
 
 // leapfrog_kr's SOLVER for samplers.HMC_random trajectories (not a C-ABI
-// solver: rhmc_hmc_random selects it).
+// solver: rhmc_hmc_random selects it), and for RHMC_random_diag's
+// (rhmc_diag_random; LeapArgsKR::diag).
 constexpr int kSolverHmcRandom = 100;
+constexpr int kSolverDiagRandom = 101;
 
 struct KRStar {  // LDS star table entry
   double f, x, y;
@@ -760,21 +763,74 @@ __device__ __forceinline__ void km_explicit_steps(double (&f)[SLOTS], double (&x
 // of the chain's stars is below the wall).  p holds the half-step momentum;
 // returns true when the last step flipped — the caller then keeps the
 // starting momentum (:547-550).  dVdq without the metric (:365-425).
-template <int SLOTS, class GRAD, bool RELOAD = false>
+// DIAG: RHMC_random_diag's trajectory instead (samplers.py:766-800; dtv
+// unused): the one step dg.dt, the drift divided by the mass matrix at the
+// flux before it, dlnDetdq + dpMpdq in the flux force (diag_force_f) from the
+// start momentum's pf^2 and px^2 + py^2, which are kept per star (p itself
+// becomes the half-step momentum), the same wall quirks, and q after every
+// step to the chain's trace rows tr [dg.rows][3K] (null: none).  The
+// pixel-major kernel (RELOAD) has no registers left for those two values (it
+// spilled): it re-reads the start momentum from p0, the chain's row of p,
+// which nothing writes before the epilogue, where the force needs it, the way
+// the steps dtv are re-read.
+template <int SLOTS, class GRAD, bool RELOAD = false, bool DIAG = false>
 __device__ __forceinline__ bool km_hmc_random_steps(double (&f)[SLOTS], double (&x)[SLOTS],
                                                     double (&y)[SLOTS], double (&pf)[SLOTS],
                                                     double (&px)[SLOTS], double (&py)[SLOTS],
                                                     const bool (&own)[SLOTS], KRStar* tab,
                                                     int n, const double* __restrict__ dtv,
-                                                    const Consts& c, GRAD grad) {
+                                                    const Consts& c, GRAD grad,
+                                                    const DiagArgs& dg = DiagArgs{},
+                                                    double* tr = nullptr, int K = 0,
+                                                    const double* __restrict__ p0 = nullptr) {
   const int m = lane_id() & 31;
   // the steps are re-read from memory (L1/L2) where used instead of being held
   // in registers across the gradient (register pressure at two slots)
   // (the index goes through an empty asm so that the loads are not hoisted)
   auto dti = [&](int t, int j) {
-    int i = 3 * (own[t] ? 32 * t + m : 0) + j;
-    asm volatile("" : "+v"(i));
-    return dtv[i];
+    if constexpr (DIAG) {
+      return dg.dt;
+    } else {
+      int i = 3 * (own[t] ? 32 * t + m : 0) + j;
+      asm volatile("" : "+v"(i));
+      return dtv[i];
+    }
+  };
+  double sf[SLOTS], sxy[SLOTS];
+  auto trace = [&](int row) {
+    if constexpr (DIAG) {
+      if (!tr || row >= dg.rows) return;
+#pragma unroll
+      for (int t = 0; t < SLOTS; ++t) {
+        if (!own[t]) continue;
+        double* r = tr + (int64_t)row * 3 * K + 3 * (32 * t + m);
+        r[0] = f[t];
+        r[1] = x[t];
+        r[2] = y[t];
+      }
+    }
+  };
+  if constexpr (DIAG) {
+    if constexpr (!RELOAD) {
+#pragma unroll
+      for (int t = 0; t < SLOTS; ++t) {
+        sf[t] = pf[t] * pf[t];
+        sxy[t] = px[t] * px[t] + py[t] * py[t];
+      }
+    }
+    trace(0);
+  }
+  auto start_sq = [&](int t, double& s_f, double& s_xy) {
+    if constexpr (RELOAD) {
+      int i = 3 * (own[t] ? 32 * t + m : 0);
+      asm volatile("" : "+v"(i));
+      const double u = p0[i], v = p0[i + 1], w = p0[i + 2];
+      s_f = u * u;
+      s_xy = v * v + w * w;
+    } else {
+      s_f = sf[t];
+      s_xy = sxy[t];
+    }
   };
   auto dtf = [&](int t) { return dti(t, 0); };
   auto dtx = [&](int t) { return dti(t, 1); };
@@ -789,6 +845,14 @@ __device__ __forceinline__ bool km_hmc_random_steps(double (&f)[SLOTS], double (
 #pragma unroll
     for (int t = 0; t < SLOTS; ++t)
       if (c.use_prior) gf[t] += c.alpha / f[t];    // :408-409
+    if constexpr (DIAG) {
+#pragma unroll
+      for (int t = 0; t < SLOTS; ++t) {
+        double s_f, s_xy;
+        start_sq(t, s_f, s_xy);
+        gf[t] = diag_force_f(gf[t], f[t], s_f, s_xy, dg.inv_f1);
+      }
+    }
   };
   kr_publish<SLOTS>(tab, f, x, y, own);
   gradient();
@@ -803,14 +867,19 @@ __device__ __forceinline__ bool km_hmc_random_steps(double (&f)[SLOTS], double (
     bool below_any = false;
 #pragma unroll
     for (int t = 0; t < SLOTS; ++t) {
-      f[t] = f[t] + dtf(t) * pf[t];                // :523
-      x[t] = x[t] + dtx(t) * px[t];
-      y[t] = y[t] + dty(t) * py[t];
+      if constexpr (DIAG) {                        // :770-771
+        diag_drift(f[t], x[t], y[t], pf[t], px[t], py[t], dg.dt, dg.inv_f1);
+      } else {
+        f[t] = f[t] + dtf(t) * pf[t];              // :523
+        x[t] = x[t] + dtx(t) * px[t];
+        y[t] = y[t] + dty(t) * py[t];
+      }
       const bool below = own[t] && f[t] < c.f_lim; // :526-529
       iflip[t] = iflip[t] || below;
       below_any = below_any || below;
     }
     flip = half_any(below_any);
+    trace(s + 1);
     kr_publish<SLOTS>(tab, f, x, y, own);
     gradient();
 #pragma unroll
@@ -921,9 +990,13 @@ leapfrog_kr(LeapArgsKR a, int f_pos) {
   if constexpr (SOLVER == RHMC_SOLVER_IMPLICIT) {
     km_steps<SLOTS>(f, x, y, pf, px, py, own, tab, a.n_steps, (double)(side - 1), c, lc, grad,
                     it_p, it_q, st);
-  } else if constexpr (SOLVER == kSolverHmcRandom) {
-    if (km_hmc_random_steps<SLOTS>(f, x, y, pf, px, py, own, tab, a.steps[chain_r], a.dtv, c,
-                                   grad)) {
+  } else if constexpr (SOLVER == kSolverHmcRandom || SOLVER == kSolverDiagRandom) {
+    constexpr bool DG = SOLVER == kSolverDiagRandom;
+    double* tr = nullptr;  // the chain's trace rows (a mirrored tail chain writes none)
+    if constexpr (DG)
+      if (a.diag.trace && chain < a.n_chains) tr = a.diag.trace + chain * a.diag.rows * 3 * K;
+    if (km_hmc_random_steps<SLOTS, decltype(grad), false, DG>(
+            f, x, y, pf, px, py, own, tab, a.steps[chain_r], a.dtv, c, grad, a.diag, tr, K)) {
       st |= RHMC_STATUS_REFLECT_F;  // p_tmp stays the starting momentum (:547-550)
 #pragma unroll
       for (int t = 0; t < SLOTS; ++t) {

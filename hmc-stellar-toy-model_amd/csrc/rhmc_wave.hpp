@@ -34,6 +34,40 @@ struct Consts {
   int counter_max, use_prior, use_Vc, pad;
 };
 
+// What samplers.lightsource_gym.RHMC_random_diag's trajectory (samplers.py:
+// 766-800) adds to an HMC_random launch: the one global step, 1/factor1 of the
+// mass matrix M = diag(1/f, f factor1, f factor1) per star (:574-600), and the
+// optional trace [n_chains][rows][3K] of q after every step (row 0: the start).
+struct DiagArgs {
+  double dt = 0.0, inv_f1 = 1.0;
+  double* trace = nullptr;
+  int32_t rows = 0, pad = 0;
+};
+
+// dVdq + dlnDetdq + dpMpdq in the flux direction (:636-664; the other
+// components of the last two are zero) from the flux gradient gf at flux f.
+// With G = 1/f, G' = -1/f^2, F = f factor1, F' = factor1:
+//   dlnDetdq_f = (G'/G + 2 F'/F)/2 = 0.5/f
+//   dpMpdq_f   = -(G' pf^2/G^2 + (px^2 + py^2) F'/F^2)/2
+//              = (sf - sxy/(factor1 f^2))/2
+// where sf = pf^2 and sxy = px^2 + py^2 are those of the momentum the
+// iteration STARTED with on every step (the reference passes p_tmp, never
+// p_half), so they are constants of a trajectory.
+__device__ __forceinline__ double diag_force_f(double gf, double f, double sf, double sxy,
+                                               double inv_f1) {
+  const double r = 1.0 / f;
+  return (gf + 0.5 * r) + 0.5 * (sf - (sxy * inv_f1) * (r * r));
+}
+
+// q + dt p_half / M with M at the position before the update (:770-771).
+__device__ __forceinline__ void diag_drift(double& f, double& x, double& y, double hf, double hx,
+                                           double hy, double dt, double inv_f1) {
+  const double im = inv_f1 / f;
+  x = x + (dt * hx) * im;
+  y = y + (dt * hy) * im;
+  f = f + (dt * hf) * f;
+}
+
 // The flux folded into a star's PSF factors (the kernels scale the column
 // factors by f, so that one product serves Lambda and the sums, and divide the
 // flux sum by f again).  At f = 0 that gives 0/0 where the reference's

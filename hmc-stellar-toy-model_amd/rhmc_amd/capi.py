@@ -63,7 +63,8 @@ EXPORTS = ("rhmc_abi_version", "rhmc_device_count", "rhmc_last_error",
            "rhmc_ragged_ok", "rhmc_leapfrog_ragged_device", "rhmc_energy_ragged_device",
            "rhmc_rows_copy_device", "rhmc_kinetic_rows_device",
            "rhmc_find_peaks", "rhmc_find_peaks_device",
-           "rhmc_dt_trials", "rhmc_dt_trials_device")
+           "rhmc_dt_trials", "rhmc_dt_trials_device",
+           "rhmc_diag_random", "rhmc_diag_random_device")
 ABI_VERSION = 4
 
 V_FLUX_WALL = 1       # rhmc_energy f_pos bits (include/rhmc.h)
@@ -136,6 +137,12 @@ def make_dt_opts(n_iter=10, grad=DT_GRAD_REFERENCE, steps_min=10, steps_max=50):
     if isinstance(grad, str):
         grad = {"reference": DT_GRAD_REFERENCE, "full": DT_GRAD_FULL}[grad]
     return DtOpts(int(n_iter), int(grad), int(steps_min), int(steps_max), (0, 0))
+
+
+class DiagOpts(ctypes.Structure):
+    """Mirror of `rhmc_diag_opts` (include/rhmc.h)."""
+    _fields_ = [("dt", ctypes.c_double), ("factor1", ctypes.c_double),
+                ("trace_rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 def make_schedule(schedule_g_ff2=None, schedule_beta=None):
@@ -242,6 +249,10 @@ def _load():
         "rhmc_dt_trials_device": (ctypes.c_int, [vp, P(RhmcParams), P(DtOpts), vp, ctypes.c_int32,
                                                  vp, vp, vp, vp, ctypes.c_int64, vp, vp, vp,
                                                  ctypes.c_uint64, vp, vp, P(DtRecord), vp]),
+        "rhmc_diag_random": (ctypes.c_int, [vp, P(RhmcParams), P(DiagOpts), vp, vp, vp,
+                                            ctypes.c_int64, ctypes.c_int32, vp, vp]),
+        "rhmc_diag_random_device": (ctypes.c_int, [vp, P(RhmcParams), P(DiagOpts), vp, vp, vp,
+                                                   ctypes.c_int64, ctypes.c_int32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -577,6 +588,49 @@ class Context:
         if single:
             q2, p2, st = q2[0], p2[0], st[0]
         return (q2, p2, st) if return_status else (q2, p2)
+
+    def diag_random(self, params, dt, factor1, q, p, steps, return_status=False, trace=False):
+        """samplers.RHMC_random_diag trajectories (rhmc_diag_random): leapfrog
+        under the mass matrix diag(1/f, f factor1, f factor1) per star with the
+        one step dt, steps[c] >= 1 steps for chain c, flux wall at
+        params.f_lim.  Returns new (q, p) (p is the input momentum on chains
+        whose last step flipped — the reference's stale-p quirk), then the
+        status words with return_status, then with trace=True q after every
+        step [n_chains, max(steps) + 1, 3K] (row 0 the start, NaN past a
+        chain's own trajectory; a 1-D q gives [steps + 1, 3K])."""
+        q2 = np.array(q, dtype=np.float64, order="C", copy=True)
+        p2 = np.array(p, dtype=np.float64, order="C", copy=True)
+        single = q2.ndim == 1
+        q2 = q2.reshape(1, -1) if single else q2.reshape(-1, q2.shape[-1])
+        p2 = p2.reshape(q2.shape)
+        K = q2.shape[1] // 3
+        st = np.zeros(q2.shape[0], np.int32)
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(steps, np.int32), (q2.shape[0],)))
+        tr, rows = None, 0
+        if trace:
+            rows = int(n.max()) + 1 if n.size else 1
+            tr = np.full((q2.shape[0], rows, 3 * K), np.nan)
+        opts = DiagOpts(float(dt), float(factor1), rows, 0)
+        vp = ctypes.c_void_p
+        _check(_lib.rhmc_diag_random(self._h, ctypes.byref(params), ctypes.byref(opts),
+                                     vp(q2.ctypes.data), vp(p2.ctypes.data), vp(n.ctypes.data),
+                                     q2.shape[0], K, vp(st.ctypes.data),
+                                     None if tr is None else vp(tr.ctypes.data)))
+        if single:
+            q2, p2, st = q2[0], p2[0], st[0]
+            tr = None if tr is None else tr[0]
+        out = (q2, p2) + ((st,) if return_status else ()) + ((tr,) if trace else ())
+        return out
+
+    def diag_random_device(self, params, dt, factor1, q_ptr, p_ptr, steps_ptr, n_chains, K,
+                           status_ptr=None, trace_ptr=None, trace_rows=0, stream=None):
+        """Device-pointer rhmc_diag_random (asynchronous on `stream`)."""
+        opts = DiagOpts(float(dt), float(factor1), int(trace_rows), 0)
+        vp = ctypes.c_void_p
+        _check(_lib.rhmc_diag_random_device(self._h, ctypes.byref(params), ctypes.byref(opts),
+                                            vp(q_ptr), vp(p_ptr), vp(steps_ptr), int(n_chains),
+                                            int(K), vp(status_ptr or 0), vp(trace_ptr or 0),
+                                            vp(stream or 0)))
 
     def find_peaks(self, params, opts, q):
         """find_peaks' seed descent (rhmc_find_peaks) on seeds q [n, 3] =

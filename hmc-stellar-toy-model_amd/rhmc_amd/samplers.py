@@ -1,7 +1,8 @@
 """The reference's older `samplers` API, routed to the MI355X engine:
 `lightsource_gym` with its three-stage pipeline — `find_peaks` (seed stars),
 `HMC_find_best_dt` (the step vector: the default branch and the step-size
-search) and unit-mass HMC (`HMC_random`).
+search) and unit-mass HMC (`HMC_random`) — and its own Riemannian sampler,
+`RHMC_random_diag` (leapfrog under the flux-dependent diagonal mass matrix).
 
 Mirrors jaekor91/HMC-stellar-toy-model `samplers.py` (file:line per method):
 same class name, attributes (set after construction, like the reference's
@@ -9,14 +10,16 @@ scripts: `gym.Nobjs`, `gym.d = 3 * Nobjs`, `gym.dt = <vector [d]>`), method
 names, argument meaning, global-NumPy-RNG draw order and results.
 
 What runs where:
-  * dVdq, V, the HMC_random trajectories, find_peaks' gradient descent of
-    the seeds and the trials of HMC_find_best_dt's search run in librhmc.so
-    (rhmc_gradient kind 0, rhmc_energy without the position check,
-    rhmc_hmc_random, rhmc_find_peaks, rhmc_dt_trials).  No CPU fallback.
-  * E, K, p_sample, the MH bookkeeping, find_peaks' seed grid and its merge of
-    near-duplicate peaks (merge_peaks), and everything between the trials of
-    the search (the coarse ladder, the bisection, the per-star Poisson
-    realisation) stay on the host (NumPy), like the reference.
+  * dVdq, V, the HMC_random and RHMC_random_diag trajectories, find_peaks'
+    gradient descent of the seeds and the trials of HMC_find_best_dt's search
+    run in librhmc.so (rhmc_gradient kind 0, rhmc_energy without the position
+    check, rhmc_hmc_random, rhmc_diag_random, rhmc_find_peaks,
+    rhmc_dt_trials).  No CPU fallback.
+  * E, K, p_sample, the MH bookkeeping, the diagonal metric's host methods
+    (compute_factors, mass_matrix, F, G, dlnDetdq, dpMpdq), find_peaks' seed
+    grid and its merge of near-duplicate peaks (merge_peaks), and everything
+    between the trials of the search (the coarse ladder, the bisection, the
+    per-star Poisson realisation) stay on the host (NumPy), like the reference.
 
 Quirks kept on purpose (samplers.py:519-552): the flux-wall flip mask is
 never cleared inside a trajectory, and a trajectory whose last step flipped
@@ -30,13 +33,23 @@ reference draw for draw from the global NumPy stream (one rhmc_dt_trials call
 per trial), rng="philox" searches all stars at once with the device's draws
 (one call per round of trials).  Without rng the call raises
 NotImplementedError, as before the search existed.
-Out of scope: RHMC_random_diag / RHMC_random, the GMM testbed and
-the plots.
+
+RHMC_random_diag (samplers.py:668-825) keeps its quirks too: dpMpdq is
+evaluated with the momentum the iteration started with on every step, the flip
+mask is sticky, a trajectory whose last step flipped keeps its starting
+momentum, and K's log-determinant is the log of a running product.  It
+requires Nchain == 1 like the reference; RHMC_random_diag_batched runs many
+chains at once and, with one chain, draws exactly what RHMC_random_diag draws.
+factor1 is computed on first use when compute_factors() has not been called.
+With save_traj, qs comes from the kernel's trace, Vs from one batched energy
+call per iteration and Ts from the host.
+Out of scope: RHMC_random (the full Hessian metric), the GMM
+testbed and the plots.
 """
 import numpy as np
 
 from . import capi
-from .photometry import (default_exp_setup, flux2mag, gauss_PSF, mag2flux,
+from .photometry import (default_exp_setup, factors, flux2mag, gauss_PSF, mag2flux,
                          poisson_realization)
 
 
@@ -170,6 +183,7 @@ class lightsource_gym(object):
         self.Nobjs = None
         self.d = None
         self.f_lim = 0.
+        self.factor0 = self.factor1 = self.factor2 = None   # compute_factors()
         self.q_seed = None
         self.peak_steps = None   # find_peaks diagnostics, per grid seed (pre-merge)
         self.peak_status = None
@@ -459,6 +473,166 @@ class lightsource_gym(object):
         E = V + np.sum(p * p, axis=1) / 2.
         E[(q[:, 0::3] < self.f_lim).any(axis=1)] = np.inf
         return E
+
+    # ------------------------------------------- the diagonal-metric sampler
+    def compute_factors(self):
+        """samplers.py:69-75."""
+        self.factor0, self.factor1, self.factor2 = factors(
+            self.num_rows, self.num_cols, self.num_rows / 2., self.num_cols / 2.,
+            self.PSF_FWHM_pix)
+
+    def F(self, f, dFdf=False):
+        """samplers.py:592-600."""
+        x1 = f * self.factor1
+        return (x1, self.factor1) if dFdf else x1
+
+    def G(self, f, dGdf=False):
+        """samplers.py:614-625."""
+        x1 = 1. / f
+        return (x1, -1 / f ** 2) if dGdf else x1
+
+    def mass_matrix(self, q):
+        """samplers.py:574-590: M = diag(G(f), F(f), F(f)) per star, q [d]."""
+        M = np.zeros_like(q)
+        for i in range(int(q.shape[0]) // 3):
+            f = q[3 * i]
+            M[3 * i] = self.G(f)
+            M[(3 * i) + 1:3 * (i + 1)] = self.F(f)
+        return M
+
+    def dlnDetdq(self, q):
+        """samplers.py:636-649."""
+        out = np.zeros_like(q)
+        for i in range(int(q.shape[0]) // 3):
+            f = q[3 * i]
+            G, dGdf = self.G(f, dGdf=True)
+            F, dFdf = self.F(f, dFdf=True)
+            out[3 * i] = 0.5 * (dGdf / G + 2 * dFdf / F)
+        return out
+
+    def dpMpdq(self, q, p):
+        """samplers.py:651-664."""
+        out = np.zeros_like(q)
+        for i in range(int(q.shape[0]) // 3):
+            f = q[3 * i]
+            pf, px, py = p[3 * i:3 * (i + 1)]
+            G, dGdf = self.G(f, dGdf=True)
+            F, dFdf = self.F(f, dFdf=True)
+            out[3 * i] = - 0.5 * (dGdf * pf ** 2 / G ** 2 + (px ** 2 + py ** 2) * dFdf / F ** 2)
+        return out
+
+    def _mass_batch(self, q):
+        """mass_matrix over chains q [n, d]."""
+        M = np.empty_like(q)
+        f = q[:, 0::3]
+        with np.errstate(all="ignore"):
+            M[:, 0::3] = 1. / f
+            M[:, 1::3] = M[:, 2::3] = f * self.factor1
+        return M
+
+    def _K_batch(self, p, M):
+        """K(p, M) per chain: a running product, then one log, like the
+        reference (an overflowing product behaves as its does)."""
+        with np.errstate(all="ignore"):
+            return (np.sum(p ** 2 / M, axis=1) + np.log(np.abs(np.prod(M, axis=1)))) / 2.
+
+    def _E_diag_batch(self, q, p, M):
+        V = self._context().energy(self._params(), q, None, f_pos=False, pos_check=False)[0]
+        E = V + self._K_batch(p, M)
+        E[(q[:, 0::3] < self.f_lim).any(axis=1)] = np.inf
+        return E
+
+    def RHMC_random_diag(self, q_model_0, Nchain=1, Niter=1000, thin_rate=0, Nwarmup=0,
+                         steps_min=10, steps_max=50, f_lim=0., f_lim_default=False,
+                         dt_global=1e-2, save_traj=False):
+        """samplers.py:668-825: leapfrog under the flux-dependent diagonal mass
+        matrix with the one step dt_global, the trajectories on the GPU
+        (rhmc_diag_random).  q_model_0 (Nobjs, 3).  Sets Nobjs, d, q_chain
+        [1, Niter+1, d], E_chain, dE_chain [1, Niter+1, 1] and A_chain [1,
+        Niter, 1]; with save_traj the lists qs, Vs, Ts (entry 0 the start, then
+        per iteration q, V(q) and K(p_start, M(q)) after every step)."""
+        assert Nchain == 1  # Currently we do not support any other.
+        self.Nchain = Nchain
+        self.Niter = Niter
+        self.thin_rate = thin_rate
+        self.Nwarmup = Nwarmup
+        self._set_f_lim(f_lim, f_lim_default)
+        if q_model_0 is None:
+            print("Use found seeds for inference.")
+            q_model_0 = self.q_seed
+        q_model_0 = np.asarray(q_model_0, dtype=float)
+        self.Nobjs = q_model_0.shape[0]
+        self.d = int(np.prod(q_model_0.shape))
+        self._run_diag(q_model_0.reshape((1, self.d)), Niter, steps_min, steps_max, dt_global,
+                       save_traj)
+        print("Chain %d Acceptance rate: %.2f%%"
+              % (0, np.sum(self.A_chain[0, :] * 100) / float(self.Niter)))
+
+    def RHMC_random_diag_batched(self, q_model_0, Niter=1000, steps_min=10, steps_max=50,
+                                 f_lim=0., f_lim_default=False, dt_global=1e-2):
+        """RHMC_random_diag over many independent chains at once (q_model_0
+        [Nchain, d]); per iteration the global NumPy RNG draws randn(Nchain, d),
+        randint(steps_min, steps_max, Nchain) and random(Nchain) — with one
+        chain exactly the reference's draws."""
+        self._set_f_lim(f_lim, f_lim_default)
+        q0 = np.asarray(q_model_0, dtype=float)
+        q0 = q0.reshape(1, -1) if q0.ndim == 1 else q0.reshape(q0.shape[0], -1)
+        self.Nchain, self.d = q0.shape
+        self.Nobjs = self.d // 3
+        self.Niter = Niter
+        self._run_diag(q0, Niter, steps_min, steps_max, dt_global, False)
+
+    def _run_diag(self, q0, Niter, steps_min, steps_max, dt_global, save_traj):
+        if getattr(self, "factor1", None) is None:
+            self.compute_factors()
+        ctx, P = self._context(), self._params()
+        n, d = q0.shape
+        self.q_chain = np.zeros((n, Niter + 1, d))
+        self.E_chain = np.zeros((n, Niter + 1, 1))
+        self.dE_chain = np.zeros((n, Niter + 1, 1))
+        self.A_chain = np.zeros((n, Niter, 1))
+        self.q_chain[:, 0, :] = q0
+        M = self._mass_batch(q0)
+        with np.errstate(all="ignore"):
+            p_initial = np.random.randn(n, d) * np.sqrt(M)
+        self.E_chain[:, 0, 0] = self._E_diag_batch(q0, p_initial, M)
+        E_previous = self.E_chain[:, 0, 0].copy()
+        q_tmp = q0.copy()
+        if save_traj:                                         # :734-737 (one chain)
+            self.qs = [np.array([q0[0]])]
+            self.Vs = [np.array([self.V(q0[0])])]
+            self.Ts = [self._K_batch(p_initial, M)]
+        for i in range(1, Niter + 1):
+            q_initial = q_tmp
+            M = self._mass_batch(q_initial)
+            with np.errstate(all="ignore"):
+                p_tmp = np.random.randn(n, d) * np.sqrt(M)
+            E_initial = self._E_diag_batch(q_tmp, p_tmp, M)
+            self.E_chain[:, i, 0] = E_initial
+            with np.errstate(invalid="ignore"):
+                self.dE_chain[:, i, 0] = E_initial - E_previous
+            steps = np.random.randint(low=steps_min, high=steps_max, size=n)
+            if save_traj:
+                q_new, p_new, trace = ctx.diag_random(P, dt_global, self.factor1, q_tmp, p_tmp,
+                                                      steps, trace=True)
+                qs = trace[0, :steps[0] + 1]
+                self.qs.append(qs)                            # one batched V per iteration
+                self.Vs.append(ctx.energy(P, qs, None, f_pos=False, pos_check=False)[0])
+                # the stale-momentum quirk: K of the START momentum at every q (:790)
+                self.Ts.append(self._K_batch(np.broadcast_to(p_tmp[0], qs.shape),
+                                             self._mass_batch(qs)))
+            else:
+                q_new, p_new = ctx.diag_random(P, dt_global, self.factor1, q_tmp, p_tmp, steps)
+            E_final = self._E_diag_batch(q_new, p_new, self._mass_batch(q_new))
+            with np.errstate(invalid="ignore"):
+                dE = E_final - E_initial
+            E_previous = E_initial
+            lnu = np.log(np.random.random(n))
+            with np.errstate(invalid="ignore"):
+                acc = (dE < 0) | (lnu < -dE)
+            self.A_chain[:, i - 1, 0] = acc
+            q_tmp = np.where(acc[:, None], q_new, q_initial)
+            self.q_chain[:, i, :] = q_tmp
 
     def _run(self, q0, Niter, steps_min, steps_max):
         n, d = q0.shape

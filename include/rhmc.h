@@ -56,6 +56,12 @@
  *       search (samplers.py:332-371): Metropolis iterations of explicit
  *       leapfrog on one star against a background image; the coarse / fine
  *       search around the trials (:327-456) stays on the host.
+ *   rhmc_diag_random / rhmc_diag_random_device
+ *       the trajectory of samplers.lightsource_gym.RHMC_random_diag
+ *       (samplers.py:766-800): explicit leapfrog under the flux-dependent
+ *       diagonal mass matrix of mass_matrix / F / G / dlnDetdq / dpMpdq
+ *       (:574-664); the momentum draw, E, K and the MH test (:719-823) stay on
+ *       the host.
  *   rhmc_params
  *       the instance attributes the step reads: dt, g_xx,
  *       g_ff, g_ff2, g0, g1, g2, B_count, f_lim, mB (-> f_low),
@@ -83,6 +89,11 @@
  *     buffer grown by another thread is released only after that launch (the
  *     order of two threads' launches on one stream is theirs to arrange).
  *     Options must not change while such calls run.  One context per GPU.
+ *     rhmc_diag_random and rhmc_diag_random_device are NOT among them (like
+ *     rhmc_hmc_random, whose plan and launch shapes they share): one thread
+ *     per context; the host-pointer call stages through the context's scratch
+ *     buffer and returns after its stream has drained, the device-pointer
+ *     call only enqueues on `stream` and reads opts before it returns.
  */
 #ifndef RHMC_H
 #define RHMC_H
@@ -367,6 +378,39 @@ int rhmc_hmc_random(rhmc_ctx* ctx, const rhmc_params* P, const double* dt, doubl
 int rhmc_hmc_random_device(rhmc_ctx* ctx, const rhmc_params* P, const double* d_dt,
                            double* d_q, double* d_p, const int32_t* d_steps, int64_t n_chains,
                            int32_t K, int32_t* d_status, void* stream);
+
+/* samplers.lightsource_gym.RHMC_random_diag's trajectory (samplers.py:766-800;
+ * the MH bookkeeping around it, :719-823, stays on the host): explicit leapfrog
+ * under the flux-dependent diagonal mass matrix M = diag(1/f, f factor1,
+ * f factor1) per star (mass_matrix / F / G, :574-634) with the one step
+ * opts->dt (the reference's dt_global) and steps[c] >= 1 steps for chain c:
+ *   p_half = p - dt/2 F(q, p),   F = dVdq + dlnDetdq + dpMpdq (:636-664)
+ *   per step: q += dt p_half / M(q before the update); p_half -= dt F(q, p)
+ *   at the end: p = p_half + dt/2 F(q, p)
+ * with the reference's quirks: dpMpdq takes the momentum the call STARTED
+ * with on every step (never p_half); the flux wall at P->f_lim behaves as in
+ * rhmc_hmc_random (sticky flip mask; when the last step flipped, p is left at
+ * its input value and the chain's status gets RHMC_STATUS_REFLECT_F); a NaN
+ * flux does not flip.  RHMC_STATUS_NONFINITE marks a non-finite result.
+ * factor1 is utils.factors()'s second value (compute_factors, :69-75).
+ * trace (nullable) [n_chains][opts->trace_rows][3K]: row t receives q after
+ * step t (row 0: the start) for t <= steps[c]; later rows are left untouched.
+ * trace_rows must exceed the longest trajectory (checked by the host-pointer
+ * call; the device-pointer call cannot read steps and writes no row past
+ * trace_rows).  q, p [n_chains][3K] updated in place; status nullable.  Only
+ * B_count, f_lim, the PSF width and the prior switch of P are read. */
+typedef struct rhmc_diag_opts {
+  double dt;          /* dt_global (finite)                            */
+  double factor1;     /* F(f) = f factor1 (finite, > 0)                */
+  int32_t trace_rows; /* rows per chain of `trace` (ignored without it) */
+  int32_t reserved;   /* must be 0                                     */
+} rhmc_diag_opts;
+int rhmc_diag_random(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* opts, double* q,
+                     double* p, const int32_t* steps, int64_t n_chains, int32_t K,
+                     int32_t* status, double* trace);
+int rhmc_diag_random_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* opts,
+                            double* d_q, double* d_p, const int32_t* d_steps, int64_t n_chains,
+                            int32_t K, int32_t* d_status, double* d_trace, void* stream);
 
 /* Per-iteration records of rhmc_mh (all nullable; host pointers for rhmc_mh,
  * device pointers for rhmc_mh_device).  Row l holds the state at the START

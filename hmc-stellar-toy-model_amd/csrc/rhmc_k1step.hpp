@@ -21,19 +21,8 @@
 namespace rhmc {
 
 // Fixed-point iterations evaluated per pass (one branch per pass).
-#ifndef RHMC_SPEC_P
-#define RHMC_SPEC_P 2
-#endif
-#ifndef RHMC_SPEC_Q
-#define RHMC_SPEC_Q 2
-#endif
-// RHMC_STATUS_NEAR_WALL in the one-star step loop: 2 = flux wall and image
-// edges, 1 = flux wall only, 0 = off.
-#ifndef RHMC_NEAR_WALL
-#define RHMC_NEAR_WALL 2
-#endif
-constexpr int kSpecP = RHMC_SPEC_P;
-constexpr int kSpecQ = RHMC_SPEC_Q;
+constexpr int kSpecP = 2;
+constexpr int kSpecQ = 2;
 
 // 1/d to within ~11 ulp (v_rcp_f64 is accurate to ~2^-24; one Newton step).
 __device__ __forceinline__ double rcp_nr1(double d) {
@@ -81,11 +70,6 @@ __device__ __forceinline__ FluxMetric flux_metric(double f, const Consts& c,
 }
 
 // Lane-parallel q-loop passes (QL = 16 lanes per chain, one DPP row).
-#ifndef RHMC_QPAR
-#define RHMC_QPAR 1
-#endif
-constexpr bool kQPar = RHMC_QPAR;
-
 __device__ __forceinline__ double row_shr1(double v) {  // lane l of a 16-lane row gets lane l - 1
   const long long b = __double_as_longlong(v);
   const int lo = __builtin_amdgcn_mov_dpp((int)b, 0x111, 0xF, 0xF, false);
@@ -201,17 +185,17 @@ __device__ __forceinline__ void k1_steps(double& f, double& x, double& y, double
       if (f < c.f_lim) {                           // :554-564
         pf = -pf;
         st |= RHMC_STATUS_REFLECT_F;
-        if (RHMC_NEAR_WALL >= 1 && f >= c.near_f) st |= RHMC_STATUS_NEAR_WALL;
+        if (f >= c.near_f) st |= RHMC_STATUS_NEAR_WALL;
       }
       if (x < 0.0 || x > edge) {
         px = -px;
         st |= RHMC_STATUS_REFLECT_XY;
-        if (RHMC_NEAR_WALL >= 2 && near_edge(x, edge)) st |= RHMC_STATUS_NEAR_WALL;
+        if (near_edge(x, edge)) st |= RHMC_STATUS_NEAR_WALL;
       }
       if (y < 0.0 || y > edge) {
         py = -py;
         st |= RHMC_STATUS_REFLECT_XY;
-        if (RHMC_NEAR_WALL >= 2 && near_edge(y, edge)) st |= RHMC_STATUS_NEAR_WALL;
+        if (near_edge(y, edge)) st |= RHMC_STATUS_NEAR_WALL;
       }
     }
     if (s == n_steps) {
@@ -264,9 +248,9 @@ __device__ __forceinline__ void k1_steps(double& f, double& x, double& y, double
       const double bf = hdt * (pf * lc.inv_gff2), cf = f + hdt * (pf * fm.A + pf * lc.c0);
       const double bx = hdt * (px * lc.inv_gxx), cx = x + hdt * (px * ihxx_s);
       const double by = hdt * (py * lc.inv_gxx), cy = y + hdt * (py * ihxx_s);
-      if constexpr (QL == 16 && kQPar) {
+      if constexpr (QL == 16) {
         q_loop_lanes16(f, x, y, bf, cf, bx, cx, by, cy, c, lc, it_q, st);
-      } else {
+      } else {  // QL == 1, the lane-group kernel: the serial loop
       bool more;
       int n = 0;
       do {

@@ -82,7 +82,7 @@ struct rhmc_ctx {
   int dt_lanes = 0;                // RHMC_OPT_DT_LANES
   void* dt_tab = nullptr;          // dt_trials' factor tables of the global-memory path
   size_t dt_tab_bytes = 0;
-  int table_mode = RHMC_TABLES_STREAM;  // RHMC_OPT_TABLES (diagnostic modes, rhmc.h)
+  int table_mode = RHMC_TABLES_STREAM;  // RHMC_OPT_TABLES
   // WinGG factor tables, one buffer per stream (work_tables).  A launch holds a
   // lease (shared_ptr) on its buffer from the lookup until the launch is
   // enqueued, so a concurrent grow on the same stream cannot free it early.
@@ -90,16 +90,9 @@ struct rhmc_ctx {
     void* p = nullptr;
     size_t bytes = 0;
     hipStream_t s = nullptr;
-    bool pooled = false;   // RHMC_TABLES_POOL*: stream-ordered, freed behind the launch
     bool synced = false;   // rhmc_ctx_destroy synchronised the device already
-    bool sync_free = false;  // pooled: wait for the stream before hipFreeAsync
     ~TabBuf() {
       if (!p) return;
-      if (pooled) {
-        if (sync_free) (void)hipStreamSynchronize(s);  // RHMC_TABLES_POOL_SYNCFREE
-        (void)hipFreeAsync(p, s);
-        return;
-      }
       if (!synced) (void)hipStreamSynchronize(s);  // the last launch reading it
       (void)hipFree(p);
     }
@@ -110,7 +103,6 @@ struct rhmc_ctx {
   };
   mutable std::mutex tab_mu;
   mutable std::vector<StreamTables> tabs;
-  mutable std::vector<std::shared_ptr<TabBuf>> kept;  // RHMC_TABLES_POOL_KEEP
 };
 
 #include "rhmc_launch.hpp"
@@ -405,16 +397,8 @@ int rhmc_ctx_set_option(rhmc_ctx* ctx, int32_t option, int32_t value) {
       ctx->window_split = value;
       return RHMC_OK;
     case RHMC_OPT_TABLES:
-      if (value < RHMC_TABLES_STREAM || value > RHMC_TABLES_POOL_BARRIER)
-        return fail(RHMC_ERR_ARG, "RHMC_OPT_TABLES must be 0 ... 6");
-#ifndef RHMC_TABLE_DIAG
-      // the stream-ordered pool modes reproduce a runtime defect (DESIGN.md
-      // section 4a: reused blocks are zeroed under a running launch); only
-      // diagnostic builds take them
-      if (value > RHMC_TABLES_STREAM_POISON)
-        return fail(RHMC_ERR_UNSUPPORTED,
-                    "RHMC_OPT_TABLES pool modes exist only in -DRHMC_TABLE_DIAG builds");
-#endif
+      if (value != RHMC_TABLES_STREAM && value != RHMC_TABLES_STREAM_POISON)
+        return fail(RHMC_ERR_ARG, "RHMC_OPT_TABLES must be 0 or 1");
       ctx->table_mode = value;
       return RHMC_OK;
     default:
@@ -452,13 +436,10 @@ void rhmc_ctx_destroy(rhmc_ctx* ctx) {
   if (ctx->mh_scratch) (void)hipFree(ctx->mh_scratch);
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->dt_tab) (void)hipFree(ctx->dt_tab);
-  if (!ctx->tabs.empty() || !ctx->kept.empty())
-    (void)hipDeviceSynchronize();   // tables may serve user streams
+  if (!ctx->tabs.empty()) (void)hipDeviceSynchronize();  // tables may serve user streams
   for (auto& t : ctx->tabs)
     if (t.buf) t.buf->synced = true;  // user streams may be gone: no per-stream sync
-  for (auto& b : ctx->kept) b->s = nullptr;  // pool frees after the device sync above
   ctx->tabs.clear();
-  ctx->kept.clear();
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -917,26 +898,4 @@ int rhmc_gen_image(rhmc_ctx* ctx, const rhmc_params* P, const double* q, int32_t
     return refresh_image_f32(ctx);
   });
 }
-
-#ifdef RHMC_TABLE_CANARY
-// Diagnostic builds only (not declared in rhmc.h): the table-region conflicts
-// seen since the last call (rhmc_windowed.hpp canary_leave: calls that saw a
-// bump, gradients / potentials that saw one, gradient / potential bumps
-// seen); resets them.
-int rhmc_debug_table_conflicts(int64_t* out5) {
-  unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tab_conflicts), sizeof(h)));
-  const unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
-  HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_tab_conflicts), z, sizeof(z)));
-  for (int i = 0; i < 5; ++i) out5[i] = (int64_t)h[i];
-  return RHMC_OK;
-}
-// The first 8 foreign header values a canary saw (raw 64-bit), [0] = how many.
-int rhmc_debug_table_seen(uint64_t* out9) {
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpyFromSymbol(out9, HIP_SYMBOL(g_tab_seen), 9 * sizeof(uint64_t)));
-  return RHMC_OK;
-}
-#endif
 }  // extern "C"

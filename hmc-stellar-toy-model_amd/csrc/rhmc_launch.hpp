@@ -60,7 +60,8 @@ int ensure_mh_scratch(rhmc_ctx* ctx, size_t bytes) {
 // stream then replaces the context's buffer, and the old one is released only
 // when its last lease goes (after a sync of its stream).  Every region a launch
 // uses is written by that launch before it is read (win_build_tables,
-// win_build_ey), which RHMC_TABLES_POISON checks.
+// win_build_ey), which RHMC_TABLES_STREAM_POISON checks by filling the buffer
+// with 0xFF bytes ahead of the launch.
 using TableLease = std::shared_ptr<rhmc_ctx::TabBuf>;
 
 int work_tables(const rhmc_ctx* ctx, int path, int K, int64_t n, hipStream_t st,
@@ -69,39 +70,7 @@ int work_tables(const rhmc_ctx* ctx, int path, int K, int64_t n, hipStream_t st,
   lease->reset();
   if (path != 0 || K < kWinGlobalFromK || n <= 0) return RHMC_OK;
   const size_t bytes = (size_t)n * WinGG::work_doubles(K) * sizeof(double);
-  const int mode = ctx->table_mode;
-  const bool poison = mode == RHMC_TABLES_STREAM_POISON || mode == RHMC_TABLES_POOL_POISON;
-  if (mode == RHMC_TABLES_POOL || mode == RHMC_TABLES_POOL_POISON ||
-      mode == RHMC_TABLES_POOL_KEEP || mode == RHMC_TABLES_POOL_SYNCFREE ||
-      mode == RHMC_TABLES_POOL_BARRIER) {
-    // Diagnostic: round 5's first scheme, one stream-ordered pool allocation
-    // per launch, released behind it (~TabBuf: hipFreeAsync on st).
-    auto b = std::make_shared<rhmc_ctx::TabBuf>();
-    b->s = st;
-    b->pooled = true;
-    b->sync_free = mode == RHMC_TABLES_POOL_SYNCFREE;
-    if (hipMallocAsync(&b->p, bytes, st) != hipSuccess) {
-      b->p = nullptr;
-      return fail(RHMC_ERR_NOMEM, "hipMallocAsync of " + std::to_string(bytes) +
-                                      " B of windowed factor tables failed");
-    }
-    b->bytes = bytes;
-    if (poison) HIP_TRY(hipMemsetAsync(b->p, 0xFF, bytes, st));
-    if (mode == RHMC_TABLES_POOL_BARRIER) {  // the launch waits for everything before it
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      HIP_TRY(hipEventRecord(e, st));
-      HIP_TRY(hipStreamWaitEvent(st, e, 0));
-      HIP_TRY(hipEventDestroy(e));
-    }
-    *out = (double*)b->p;
-    if (mode == RHMC_TABLES_POOL_KEEP) {  // never reused: released at rhmc_ctx_destroy
-      std::lock_guard<std::mutex> lk(ctx->tab_mu);
-      ctx->kept.push_back(b);
-    }
-    *lease = std::move(b);
-    return RHMC_OK;
-  }
+  const bool poison = ctx->table_mode == RHMC_TABLES_STREAM_POISON;
   std::lock_guard<std::mutex> lk(ctx->tab_mu);
   rhmc_ctx::StreamTables* t = nullptr;
   for (auto& e : ctx->tabs)
@@ -292,44 +261,30 @@ int with_slots(int K, F&& f) {
     default: return f(TypeTag<G>{}, IntTag<4>{});
   }
 }
-// K >= kWinGlobalFromK on the windowed path: the global-table policy (the
-// only policy instantiated past 256 stars, 8 or 16 slots)
+// K >= kWinGlobalFromK on the windowed path: the global-table policy, two
+// slots and up (the only policy instantiated past 256 stars, 8 or 16 slots)
+static_assert(kWinGlobalFromK == 65, "below it one slot (64 stars) of LDS tables");
 template <class F>
 int with_big(int K, F&& f) {
-  if constexpr (kWinGlobalFromK <= 64 * 2)
-    if (K <= 128) return f(TypeTag<WinGG>{}, IntTag<2>{});
-  if constexpr (kWinGlobalFromK <= 64 * 4)
-    if (K <= 256) return f(TypeTag<WinGG>{}, IntTag<4>{});
+  if (K <= 128) return f(TypeTag<WinGG>{}, IntTag<2>{});
+  if (K <= 256) return f(TypeTag<WinGG>{}, IntTag<4>{});
   if (K <= 512) return f(TypeTag<WinGG>{}, IntTag<8>{});
   return f(TypeTag<WinGG>{}, IntTag<16>{});
 }
-// LDS-table policies below kWinGlobalFromK (windowed) / 256 (dense)
-template <class G, class F>
-int with_slots_lds(int K, F&& f) {
-  if (K <= 64) return f(TypeTag<G>{}, IntTag<1>{});
-  if constexpr (kWinGlobalFromK > 65 || !std::is_same<G, WinG>::value)
-    if (K <= 128) return f(TypeTag<G>{}, IntTag<2>{});
-  if constexpr (kWinGlobalFromK > 129 || !std::is_same<G, WinG>::value)
-    return f(TypeTag<G>{}, IntTag<4>{});
-  return fail(RHMC_ERR_ARG, "no LDS-table slotted kernel for K = " + std::to_string(K));
-}
+// Windowed: LDS tables (WinG) in one slot below kWinGlobalFromK stars
 template <class F>
 int with_path(int path, int K, F&& f) {
   if (path == 32) return with_slots<DenseG<32>>(K, f);  // dense_path: K <= 256
   if (path == 48) return with_slots<DenseG<48>>(K, f);
   if (K >= kWinGlobalFromK) return with_big(K, f);
-  return with_slots_lds<WinG>(K, f);
+  return f(TypeTag<WinG>{}, IntTag<1>{});
 }
 // The windowed energy kernel's policy: column tables only (WinEG) below
 // kWinGlobalFromK, the global tables from there
 template <class F>
 int with_energy_win(int K, F&& f) {
   if (K >= kWinGlobalFromK) return with_big(K, f);
-  if (K <= 64) return f(TypeTag<WinEG>{}, IntTag<1>{});
-  if constexpr (kWinGlobalFromK > 65)
-    if (K <= 128) return f(TypeTag<WinEG>{}, IntTag<2>{});
-  if constexpr (kWinGlobalFromK > 129) return f(TypeTag<WinEG>{}, IntTag<4>{});
-  return fail(RHMC_ERR_ARG, "no LDS-table energy kernel for K = " + std::to_string(K));
+  return f(TypeTag<WinEG>{}, IntTag<1>{});
 }
 
 // ---------------------------------------------------------------------------

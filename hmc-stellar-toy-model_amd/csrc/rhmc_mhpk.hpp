@@ -39,7 +39,7 @@ struct MhKArgs {
 
 template <int IMG, int KMAX>
 struct MhPK {
-  using PK = PixK<IMG, KMAX, RHMC_PK_CT>;
+  using PK = PixK<IMG, KMAX>;
   // LDS: the pixel-major kernel's (exp table, star tables, factor tables,
   // image).
   static __host__ __device__ constexpr size_t lds_bytes(int waves) {

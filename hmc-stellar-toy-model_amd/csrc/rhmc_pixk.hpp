@@ -28,21 +28,6 @@
 
 namespace rhmc {
 
-// Image columns per pass of the pixel-major gradient (1 to 3; capped at the
-// lane's column count).
-#ifndef RHMC_PK_CT
-#define RHMC_PK_CT 3
-#endif
-// Factor tables by recurrence (PixK::tables_rec; 0: one exp per entry).
-#ifndef RHMC_PK_REC
-#define RHMC_PK_REC 1
-#endif
-// The 3 KMAX per-star sums by one 32-lane reduce-scatter (0: one all-reduce
-// per sum).
-#ifndef RHMC_PK_RS
-#define RHMC_PK_RS 1
-#endif
-
 // v with the double's halves through update_dpp: lanes of the banks in
 // BANKS take src moved by CTRL, the others keep old.
 template <int CTRL, int BANKS>
@@ -102,7 +87,9 @@ __device__ __forceinline__ double reduce_scatter32(const double (&v)[32]) {
   return keep + dpp_move<0xB1>(send);  // xor 1: quad_perm [1,0,3,2]
 }
 
-template <int IMG, int KMAX, int CT_ = RHMC_PK_CT>
+// CT_: image columns per pass of the pixel-major gradient (1 to 3; capped at
+// the lane's column count).
+template <int IMG, int KMAX, int CT_ = 3>
 struct PixK {
   static constexpr int LPC = 32;           // lanes per chain
   static constexpr int CPW = kWave / LPC;  // chains per wave
@@ -154,11 +141,7 @@ struct PixK {
       }
     const double* rt = rtab + (size_t)rh * KMAX;          // row 2 r + rh
     const float* dp = simg + (rh * 16 + cg) * NCP + ci0;
-// rows per loop iteration
-#ifndef RHMC_PK_ROW_UNROLL
-#define RHMC_PK_ROW_UNROLL 4
-#endif
-#pragma unroll RHMC_PK_ROW_UNROLL
+#pragma unroll 4
     for (int r = 0; r < NR; ++r) {
       double ex[KMAX];
 #pragma unroll
@@ -281,9 +264,7 @@ struct PixK {
                                                 const KRStar* tab, double* rtab, double* ctab,
                                                 int K, const LeanConsts& lc) {
     const int m = lane_id() & (LPC - 1);
-#if RHMC_PK_REC
     if (!tables_rec(etab, tab, rtab, ctab, K, lc))
-#endif
     for (int e = m; e < IMG * KMAX; e += LPC) {
       const int i = e / KMAX, k = e - (e / KMAX) * KMAX;
       double ex = 0.0, fey = 0.0;
@@ -318,9 +299,8 @@ struct PixK {
       columns<CT>(ci, simg, rtab, ctab, K, c, A0, A1, A2);
     if constexpr (NC % CT == 1) columns<1>(NC - 1, simg, rtab, ctab, K, c, A0, A1, A2);
     static_assert(NC % CT <= 1, "column passes");
-#if RHMC_PK_RS
-    // star k's sums land in lanes k, KMAX + k, 2 KMAX + k (phantom stars' A
-    // are zero)
+    // The 3 KMAX per-star sums by one 32-lane reduce-scatter: star k's sums
+    // land in lanes k, KMAX + k, 2 KMAX + k (phantom stars' A are zero)
     static_assert(3 * KMAX <= 32, "one reduce-scatter slot per sum");
     double v[32];
 #pragma unroll
@@ -337,23 +317,6 @@ struct PixK {
       gx = -fma(kCtr - st.x, s0, s1) * lc.inv_var;          // :405
       gy = -fma(kCtr - st.y, s0, s2) * lc.inv_var;          // :406
     }
-#else  // (K wave-uniform here: not for ragged sets, whose two chains may differ)
-    gf = gx = gy = 0.0;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      if (k < K) {  // wave-uniform
-        const double s0 = half_sum_dpp(A0[k]);
-        const double s1 = half_sum_dpp(A1[k]);
-        const double s2 = half_sum_dpp(A2[k]);
-        if (m == k) {
-          const KRStar st = tab[k];
-          gf = -s0 / st.pad;                                // :404 (pad = flux_fold(f))
-          gx = -fma(kCtr - st.x, s0, s1) * lc.inv_var;      // :405
-          gy = -fma(kCtr - st.y, s0, s2) * lc.inv_var;      // :406
-        }
-      }
-    }
-#endif
   }
 };
 
@@ -370,9 +333,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 leapfrog_pk(LeapArgsKR a, int f_pos) {
   // (HMC_random ran two columns per pass until the unguarded accumulation
   // freed the registers three need)
-  // The all-reduce gradient (RHMC_PK_RS = 0) assumes one K per wave.
-  static_assert(!RAGGED || RHMC_PK_RS, "ragged pixel-major launches need the reduce-scatter");
-  using PK = PixK<IMG, KMAX, RHMC_PK_CT>;
+  using PK = PixK<IMG, KMAX>;
   extern __shared__ double lds[];
   const int W = blockDim.x / kWave;
   exp_tab_fill(lds);

@@ -40,12 +40,7 @@ constexpr int kMaxK = 1024;        // slotted kernels, global tables (WinGG): 8 
 // The windowed path's first star count on the global-table policy (WinGG)
 // instead of LDS tables (WinG, whose 2 K 33 doubles per wave cap a CU at one
 // or two waves past 64 stars)
-#ifndef RHMC_WINGG_FROM
-#define RHMC_WINGG_FROM 65
-#endif
-constexpr int kWinGlobalFromK = RHMC_WINGG_FROM;
-static_assert(kWinGlobalFromK == 65 || kWinGlobalFromK == 129 || kWinGlobalFromK == 257,
-              "a register-slot boundary");
+constexpr int kWinGlobalFromK = 65;
 
 // Star slots per lane of the slotted kernels for K stars.
 constexpr int win_slots(int K) {

@@ -39,16 +39,6 @@
 
 namespace rhmc {
 
-#ifndef RHMC_LANE_QUAD_RCP
-#define RHMC_LANE_QUAD_RCP 1
-#endif
-constexpr bool kQuadRcp = RHMC_LANE_QUAD_RCP;  // A/B knob (tools/variants)
-// PSF factors by recurrence (0: one exp per row and per column)
-#ifndef RHMC_LANE_REC
-#define RHMC_LANE_REC 1
-#endif
-constexpr bool kLaneRec = RHMC_LANE_REC;
-
 template <typename DT>
 struct Vec16;
 template <>
@@ -97,7 +87,7 @@ struct TiledL {
 
   // The chain's sums of dphidq pixel terms over its window (every lane of the
   // group gets them): s0 = sum psf s, s1 = sum psf s dx, s2 = sum psf s dy.
-  // PSF factors by recurrence (RHMC_LANE_REC; utils.py:475-486 as in
+  // PSF factors by recurrence (utils.py:475-486 as in
   // PixK::tables_rec): runs of kRun entries start from two exps,
   //   e(v) = exp(-c v^2),  g(v) = exp(-c (2 s v + s^2)),  e(v + s) = e(v) g(v),
   //   g(v + s) = g(v) exp(-2 c s^2)
@@ -121,8 +111,8 @@ struct TiledL {
     const double vfirst = ((double)c0 + 0.5) - y, vlast = ((double)(c0 + WIN - 1) + 0.5) - y;
     const double ufirst = ((double)(r0 + g) + 0.5) - x;
     const double ulast = ((double)(r0 + g + LPC * (NR - 1)) + 0.5) - x;
-    const bool rec_c = kLaneRec && fabs(vfirst) < lc.rec_vmax && fabs(vlast) < lc.rec_vmax;
-    const bool rec_r = kLaneRec && fabs(ufirst) < lc.rec_vmax && fabs(ulast) < lc.rec_vmax;
+    const bool rec_c = fabs(vfirst) < lc.rec_vmax && fabs(vlast) < lc.rec_vmax;
+    const bool rec_r = fabs(ufirst) < lc.rec_vmax && fabs(ulast) < lc.rec_vmax;
     double ey[WIN], ew[WIN];
     if (rec_c) {
 #pragma unroll
@@ -175,7 +165,7 @@ struct TiledL {
 #pragma unroll
       for (int jv = 0; jv < WIN / NV; ++jv) {
         const V d = row[jv * NV];
-        if constexpr (kQuadRcp && NV == 4) {
+        if constexpr (NV == 4) {
           // one v_rcp_f64 per 4 pixels: 1/(l0 l1 l2 l3), then the pair
           // reciprocals and the single ones by products (Lambda >= B > 0)
           const int j = jv * NV;
@@ -188,7 +178,7 @@ struct TiledL {
           acc(j + 1, fma((double)d[1], l0 * r01, -1.0));
           acc(j + 2, fma((double)d[2], l3 * r23, -1.0));
           acc(j + 3, fma((double)d[3], l2 * r23, -1.0));
-        } else {
+        } else {  // the fp64 image: one reciprocal per pixel pair
 #pragma unroll
           for (int k = 0; k < NV; k += 2) {
             const int j = jv * NV + k;

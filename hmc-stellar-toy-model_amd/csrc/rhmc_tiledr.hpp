@@ -49,43 +49,23 @@ __device__ __forceinline__ double swizzle_d(double v) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-// Pixels sharing one v_rcp_f64 in the pixel loop (2 or 4).
-#ifndef RHMC_RCP_GROUP
-#define RHMC_RCP_GROUP 4
-#endif
-constexpr int kRcpGroup = RHMC_RCP_GROUP;
-
-// PSF factors by recurrence (factors_rec; 0: four exps per lane, factors).
-#ifndef RHMC_FACT_REC
-#define RHMC_FACT_REC 1
-#endif
-
-// Fold each row sum R_i into the moments as soon as its row is complete
-// (same summation order; frees the row-sum registers during the pixel loop).
-#ifndef RHMC_RFOLD
-#define RHMC_RFOLD 1
-#endif
+// Pixels sharing one v_rcp_f64 in the pixel loop.
+constexpr int kRcpGroup = 4;
 
 // DT: the type the window pixels are cached in (float when the image is
-// exactly representable in fp32, else double).
-//
-// ROW0 / TR select a row slice of the window for this wave: lane row a owns
-// window rows ROW0 + a TR .. + TR - 1 (the whole window: ROW0 = 0, TR = WIN/4).
-// A two-wave split (rows 0-11 with the serial step on one wave, rows 12-27 on
-// a helper wave, two workgroup barriers per step) was measured at 0.8x of the
-// single-wave kernel at 4096 chains and dropped.
-template <int IMG, int WIN, typename DT, int ROW0 = 0, int TR_ = WIN / 4>
+// exactly representable in fp32, else double).  Lane row a owns window rows
+// a TR .. a TR + TR - 1.
+template <int IMG, int WIN, typename DT>
 struct TiledR {
   static constexpr int LPC = 16;           // lanes per chain
   static constexpr int CPW = kWave / LPC;  // chains per wave
   static constexpr int P = IMG + 1;        // LDS row pitch
-  static constexpr int TR = TR_;           // window rows per lane
+  static constexpr int TR = WIN / 4;       // window rows per lane
   static constexpr int TC = WIN / 4;       // window columns per lane
   static constexpr int NPX = TR * TC;
   static constexpr int NTR = (TR + 3) / 4; // row factors evaluated per lane
   static_assert(WIN == 28 || WIN == 32, "window side");
   static_assert(IMG >= WIN, "window inside the image");
-  static_assert(ROW0 + 4 * TR <= WIN && TR <= 8, "row slice inside the window");
 
   // LDS: the exp table (64 doubles), then the image as DT [IMG][P].
   static __host__ __device__ constexpr size_t lds_bytes() {
@@ -150,7 +130,7 @@ struct TiledR {
     const bool stay = x >= k.xlo && x < k.xhi && y >= k.ylo && y < k.yhi;
     if (__builtin_amdgcn_ballot_w64(!stay) != 0) {
       const int r0 = origin(x), c0 = origin(y);
-      const DT* base = sD + (r0 + ROW0 + TR * a) * P + c0 + b;
+      const DT* base = sD + (r0 + TR * a) * P + c0 + b;
 #pragma unroll
       for (int i = 0; i < TR; ++i)
 #pragma unroll
@@ -175,7 +155,7 @@ struct TiledR {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       if (t < NTR) {
-        const double er = (double)(ROW0 + TR * a + b + 4 * t) + 0.5;  // exact: (r0 + e) + .5
+        const double er = (double)(TR * a + b + 4 * t) + 0.5;  // exact: (r0 + e) + .5
         const double vr = (r0 + er) - x;
         rv[t] = exp_neg(-(vr * vr) * lc.inv_two_sig2, etab);
       }
@@ -216,18 +196,16 @@ struct TiledR {
                                                      const Cache& k, double x, double y,
                                                      const LeanConsts& lc, double scale,
                                                      double (&ex)[TR], double (&ey)[TC]) {
-#if RHMC_FACT_REC
     const int lane = lane_id();
     const int m = lane % LPC;
     const int a = m / 4;
-    const double v0 = (k.r0 + ((double)(ROW0 + TR * a) + 0.5)) - x;  // row group a, first row
+    const double v0 = (k.r0 + ((double)(TR * a) + 0.5)) - x;  // row group a, first row
     const double w0 = (k.c0 + ((double)a + 0.5)) - y;                // column a
     const bool ok = fabs(v0) < lc.rec_vmax && fabs(w0) < lc.rec_vmax;
     if (__builtin_amdgcn_ballot_w64(!ok) == 0) {
       factors_from(etab, v0, w0, lc, scale, ex, ey);
       return;
     }
-#endif
     factors(etab, k, x, y, lc, ex, ey);
 #pragma unroll
     for (int j = 0; j < TC; ++j) ey[j] = scale * ey[j];
@@ -296,7 +274,7 @@ struct TiledR {
     return group_sum(v);
   }
 
-  // The row slice's sums of the chain's dphidq pixel terms, all three scaled
+  // The window's sums of the chain's dphidq pixel terms, all three scaled
   // by the flux fs = flux_fold(f) (out): s0 = fs sum psf s, s1 = fs sum psf s dx,
   // s2 = fs sum psf s dy
   // (s = D/Lambda - 1; every lane of the chain gets them).  The column
@@ -334,11 +312,13 @@ struct TiledR {
     // s_ij = D_ij / Lambda_ij - 1 with one reciprocal per group of kRcpGroup
     // pixels (row-major): 1/(l0 l1 l2 l3) by v_rcp_f64 + one Newton step, then
     // 1/l0 = l1 l2 l3 r etc. by products (v_rcp_f64 issues at a quarter of the
-    // FMA rate); then the separable row / column sums (rhmc_tiled2.hpp).
+    // FMA rate); then the separable row / column sums.
     double R[TR], C[TC];
     // a0 = sum_i ex_i R_i is also sum_j fey_j C_j: it serves both moments
     double a0 = 0.0, a1 = 0.0, w1 = 0.0;
-    auto fold = [&](int i) {  // row i's sum into the moments (in row order)
+    // row i's sum into the moments as soon as the row is complete (in row
+    // order; frees the row-sum registers during the pixel loop)
+    auto fold = [&](int i) {
       const double tt = ex[i] * R[i];
       a0 += tt;
       if (i > 0) a1 = fma(tt, (double)i, a1);
@@ -350,31 +330,25 @@ struct TiledR {
       const int i = pp / TC, j = pp % TC;
       R[i] = (j == 0) ? ey[j] * sv : fma(ey[j], sv, R[i]);
       C[j] = (i == 0) ? ex[i] * sv : fma(ex[i], sv, C[j]);
-      if (RHMC_RFOLD && j == TC - 1) fold(i);
+      if (j == TC - 1) fold(i);
     };
     auto rcpn = [](double L) {
       const double r = __builtin_amdgcn_rcp(L);
       return fma(r, fma(-L, r, 1.0), r);
     };
     constexpr int G = kRcpGroup;
+    static_assert(G == 4, "the pixel loop takes four pixels per reciprocal");
     constexpr int NG = NPX / G * G;
 #pragma unroll
     for (int pp = 0; pp < NG; pp += G) {
-      if constexpr (G == 4) {
-        const double l0 = lam(pp), l1 = lam(pp + 1), l2 = lam(pp + 2), l3 = lam(pp + 3);
-        const double l01 = l0 * l1, l23 = l2 * l3;
-        const double r = rcpn(l01 * l23);
-        const double r01 = l23 * r, r23 = l01 * r;
-        acc(pp, fma((double)k.d[pp], l1 * r01, -1.0));
-        acc(pp + 1, fma((double)k.d[pp + 1], l0 * r01, -1.0));
-        acc(pp + 2, fma((double)k.d[pp + 2], l3 * r23, -1.0));
-        acc(pp + 3, fma((double)k.d[pp + 3], l2 * r23, -1.0));
-      } else {
-        const double l0 = lam(pp), l1 = lam(pp + 1);
-        const double r = rcpn(l0 * l1);
-        acc(pp, fma((double)k.d[pp], l1 * r, -1.0));
-        acc(pp + 1, fma((double)k.d[pp + 1], l0 * r, -1.0));
-      }
+      const double l0 = lam(pp), l1 = lam(pp + 1), l2 = lam(pp + 2), l3 = lam(pp + 3);
+      const double l01 = l0 * l1, l23 = l2 * l3;
+      const double r = rcpn(l01 * l23);
+      const double r01 = l23 * r, r23 = l01 * r;
+      acc(pp, fma((double)k.d[pp], l1 * r01, -1.0));
+      acc(pp + 1, fma((double)k.d[pp + 1], l0 * r01, -1.0));
+      acc(pp + 2, fma((double)k.d[pp + 2], l3 * r23, -1.0));
+      acc(pp + 3, fma((double)k.d[pp + 3], l2 * r23, -1.0));
     }
     if constexpr (NPX - NG >= 2) {
       constexpr int pp = NG;
@@ -388,13 +362,9 @@ struct TiledR {
       acc(pp, fma((double)k.d[pp], rcpn(lam(pp)), -1.0));
     }
     gmark(1);
-    if (!RHMC_RFOLD) {
-#pragma unroll
-      for (int i = 0; i < TR; ++i) fold(i);
-    }
 #pragma unroll
     for (int j = 1; j < TC; ++j) w1 = fma(ey[j] * C[j], (double)(4 * j), w1);
-    const double dxa = ((r0 + (double)(ROW0 + TR * a)) - x) + 0.5;  // lane's row 0 offset
+    const double dxa = ((r0 + (double)(TR * a)) - x) + 0.5;  // lane's row 0 offset
     const double dyb = ((c0 + (double)b) - y) + 0.5;                // lane's column 0 offset
     s0 = group_sum(a0);
     s1 = group_sum(fma(dxa, a0, a1));
@@ -405,8 +375,8 @@ struct TiledR {
     }
   }
 
-  // Pixel part of the chain's dphidq over the slice (the whole window for the
-  // default slice).  partial's sums carry f: gx, gy need no f, gf one 1/f.
+  // Pixel part of the chain's dphidq over the window.  partial's sums carry f:
+  // gx, gy need no f, gf one 1/f.
   template <bool PROFG = false>
   static __device__ __forceinline__ void gradient(const double* __restrict__ etab,
                                                   const DT* __restrict__ sD, Cache& k,

@@ -70,25 +70,10 @@ struct KRStar {  // LDS star table entry
   double pad;     // flux_fold(f): the flux the pixel-major kernel folds into its factors
 };
 
-// TAB variant: Lambda over all stars in an unrolled loop (A/B knob), for at
-// most TABK stars (kr_tables in rhmc_select.hpp: K <= 16).
-#ifndef RHMC_KR_ALLSTARS
-#define RHMC_KR_ALLSTARS 1
-#endif
-constexpr bool kAllStarsTab = RHMC_KR_ALLSTARS;
+// TAB variant: Lambda over all stars in an unrolled loop, for at most TABK
+// stars (kr_tables in rhmc_select.hpp: K <= 16), and the image staged in LDS
+// instead of read from L2.
 constexpr int TABK = 16;
-// TAB variant: the image staged in LDS instead of read from L2 (A/B knob).
-#ifndef RHMC_KR_IMG_LDS
-#define RHMC_KR_IMG_LDS 1
-#endif
-constexpr bool kImgLds = RHMC_KR_IMG_LDS;
-// Window-major variant without tables (C5): the three per-window sums go to a
-// per-chain LDS buffer and are reduced 8 windows at a time (0: three 32-lane
-// all-reduces per window).
-#ifndef RHMC_KR_DEFER
-#define RHMC_KR_DEFER 1
-#endif
-constexpr bool kDeferRed = RHMC_KR_DEFER;
 
 // This chain's half of a wave ballot (lanes 0-31 or 32-63).
 __device__ __forceinline__ bool half_any(bool v) {
@@ -112,10 +97,12 @@ struct TiledRK {
   static_assert(SLOTS == 1 || SLOTS == 2, "K <= 64");
   // all-stars Lambda loop: fp32-image variant only (the fp64-image one would
   // spill: its window pixels take twice the registers)
-  static constexpr bool kAll = TAB && kAllStarsTab && sizeof(DT) == sizeof(float);
-  // deferred sums: [8 windows x 3 sums] rows of RP doubles (32 lanes + pad:
-  // 16-byte aligned rows, rows 4 banks apart)
-  static constexpr bool kDefer = !TAB && kDeferRed;
+  static constexpr bool kAll = TAB && sizeof(DT) == sizeof(float);
+  // deferred sums (the window-major variant without tables, C5): the three
+  // per-window sums go to a per-chain LDS buffer and are reduced 8 windows at
+  // a time: [8 windows x 3 sums] rows of RP doubles (32 lanes + pad: 16-byte
+  // aligned rows, rows 4 banks apart)
+  static constexpr bool kDefer = !TAB;
   static constexpr int RB = 8, RP = 34;
   static constexpr int RED_DOUBLES = kDefer ? RB * 3 * RP : 0;
 
@@ -130,7 +117,7 @@ struct TiledRK {
                                                         int ws = 1) {
     return kExpTab * sizeof(double) + (size_t)waves * CPW * KMAX * sizeof(KRStar) +
            (TAB ? (size_t)waves * CPW * K * 2 * side * sizeof(double) +
-                      (kImgLds ? (size_t)side * side * sizeof(DT) : 0)
+                      (size_t)side * side * sizeof(DT)
                 : (size_t)waves * CPW * RED_DOUBLES * sizeof(double)) +
            xchg_doubles(waves, ws) * sizeof(double);
   }
@@ -325,31 +312,24 @@ struct TiledRK {
         double ex[TR], ey[TC];
         star_factors(etab, ftab, side, k, sk, R0, C0, a, b, lc, ex, ey);
         if constexpr (!kAll) add_star(sk.f, ex, ey);
-        // s = D/Lambda - 1, one reciprocal per pixel pair (rhmc_tiledr.hpp)
+        // s = D/Lambda - 1, one v_rcp_f64 per 4 pixels (rhmc_tiledr.hpp)
         double R[TR], C[TC];
         auto acc = [&](int pp, double sv) {
           const int i = pp / TC, j = pp % TC;
           R[i] = (j == 0) ? ey[j] * sv : fma(ey[j], sv, R[i]);
           C[j] = (i == 0) ? ex[i] * sv : fma(ex[i], sv, C[j]);
         };
-        static_assert(NPX % 4 == 0, "pixel groups of four");
+        static_assert(NPX % 4 == 0 && kRcpGroup == 4, "pixel groups of four");
 #pragma unroll
         for (int pp = 0; pp < NPX; pp += kRcpGroup) {
-          if constexpr (kRcpGroup == 4) {  // one v_rcp_f64 per 4 pixels (rhmc_tiledr.hpp)
-            const double l0 = lam[pp], l1 = lam[pp + 1], l2 = lam[pp + 2], l3 = lam[pp + 3];
-            const double l01 = l0 * l1, l23 = l2 * l3;
-            const double r = rcp_nr1(l01 * l23);
-            const double r01 = l23 * r, r23 = l01 * r;
-            acc(pp, fma((double)d[pp], l1 * r01, -1.0));
-            acc(pp + 1, fma((double)d[pp + 1], l0 * r01, -1.0));
-            acc(pp + 2, fma((double)d[pp + 2], l3 * r23, -1.0));
-            acc(pp + 3, fma((double)d[pp + 3], l2 * r23, -1.0));
-          } else {
-            const double l0 = lam[pp], l1 = lam[pp + 1];
-            const double r = rcp_nr1(l0 * l1);
-            acc(pp, fma((double)d[pp], l1 * r, -1.0));
-            acc(pp + 1, fma((double)d[pp + 1], l0 * r, -1.0));
-          }
+          const double l0 = lam[pp], l1 = lam[pp + 1], l2 = lam[pp + 2], l3 = lam[pp + 3];
+          const double l01 = l0 * l1, l23 = l2 * l3;
+          const double r = rcp_nr1(l01 * l23);
+          const double r01 = l23 * r, r23 = l01 * r;
+          acc(pp, fma((double)d[pp], l1 * r01, -1.0));
+          acc(pp + 1, fma((double)d[pp + 1], l0 * r01, -1.0));
+          acc(pp + 2, fma((double)d[pp + 2], l3 * r23, -1.0));
+          acc(pp + 3, fma((double)d[pp + 3], l2 * r23, -1.0));
         }
         double a0 = 0.0, a1 = 0.0, w0 = 0.0, w1 = 0.0;
 #pragma unroll
@@ -923,7 +903,7 @@ leapfrog_kr(LeapArgsKR a, int f_pos) {
   if constexpr (sizeof(DT) == sizeof(float)) img = reinterpret_cast<const DT*>(a.Df);
   else img = reinterpret_cast<const DT*>(a.D);
   exp_tab_fill(lds);
-  if constexpr (TAB && kImgLds) {  // image after the factor tables (lds_bytes)
+  if constexpr (TAB) {  // image after the factor tables (lds_bytes)
     const int nw = blockDim.x / kWave;
     DT* simg = reinterpret_cast<DT*>(
         lds + kExpTab + (size_t)nw * TK::CPW * TK::KMAX * (sizeof(KRStar) / 8) +

@@ -67,47 +67,6 @@ __device__ __forceinline__ void tab_sync() {
   }
 }
 
-// Diagnostic build (-DRHMC_TABLE_CANARY, never the product library): each
-// wave's global table region starts with a 64-bit counter to which lane 0 adds
-// the call's tag when a gradient (tag 1) or potential (tag 2^32) starts and
-// again when it ends; anything else that bumped it in between (another call
-// in the same region at the same time) is counted in g_tab_conflicts:
-// [0] calls that saw a bump, [1] / [2] gradients / potentials that saw one,
-// [3] / [4] the gradient / potential bumps they saw (enter + leave of every
-// foreign call); rhmc_debug_table_conflicts() reads them.  Other writers
-// (not tagged) show as a bump of neither kind.
-#ifdef RHMC_TABLE_CANARY
-#ifndef RHMC_TABLE_DIAG
-#define RHMC_TABLE_DIAG 1  // the pool modes of RHMC_OPT_TABLES
-#endif
-constexpr int kTabHeader = 8;  // doubles before a wave's tables
-__device__ unsigned long long g_tab_conflicts[6];
-__device__ unsigned long long g_tab_seen[9];  // [0] count, then the first 8 foreign header values
-__device__ __forceinline__ unsigned long long canary_enter(double* hdr, int kind) {
-  unsigned long long v = 0;
-  const unsigned long long tag = kind == 1 ? 1ull : (1ull << 32);
-  if (lane_id() == 0) v = atomicAdd((unsigned long long*)hdr, tag);
-  return v;
-}
-__device__ __forceinline__ void canary_leave(double* hdr, unsigned long long v, int kind) {
-  if (lane_id() == 0) {
-    const unsigned long long tag = kind == 1 ? 1ull : (1ull << 32);
-    const unsigned long long now = atomicAdd((unsigned long long*)hdr, tag);
-    if (now != v + tag) {
-      const unsigned long long d = now - (v + tag);
-      atomicAdd(&g_tab_conflicts[0], 1ull);
-      atomicAdd(&g_tab_conflicts[kind], 1ull);
-      atomicAdd(&g_tab_conflicts[3], d & 0xffffffffull);
-      atomicAdd(&g_tab_conflicts[4], d >> 32);
-      const unsigned long long slot = atomicAdd(&g_tab_seen[0], 1ull);
-      if (slot < 8ull) atomicExch(&g_tab_seen[1 + slot], now);
-    }
-  }
-}
-#else
-constexpr int kTabHeader = 0;
-#endif
-
 // Does lane `lane` hold a star in slot t?
 __device__ __forceinline__ bool win_own(int t, int K) { return kWave * t + lane_id() < K; }
 
@@ -188,9 +147,6 @@ __device__ void win_gradient(const double* __restrict__ D, const WinTables& t, i
                              const LeanConsts& lc, bool with_metric, double (&gf)[SLOTS],
                              double (&gx)[SLOTS], double (&gy)[SLOTS]) {
   const int lane = lane_id();
-#ifdef RHMC_TABLE_CANARY
-  const unsigned long long cv = GT ? canary_enter(t.ex - kTabHeader, 1) : 0ull;
-#endif
   int bx[SLOTS], by[SLOTS];
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
@@ -292,9 +248,6 @@ __device__ void win_gradient(const double* __restrict__ D, const WinTables& t, i
   }
   if (c.use_Vc) vc_gradient<SLOTS>(K, x, y, c, gx, gy);     // :411-418
   tab_sync<GT>();
-#ifdef RHMC_TABLE_CANARY
-  if (GT) canary_leave(t.ex - kTabHeader, cv, 1);
-#endif
 }
 
 // Column factor tables only (the potential's; the row factors are per-row
@@ -375,9 +328,6 @@ __device__ double win_potential(const double* __restrict__ D, double* ey,
                                 const LeanConsts& lc) {
   constexpr int R = kPotRows;
   const int lane = lane_id();
-#ifdef RHMC_TABLE_CANARY
-  const unsigned long long cv = GT ? canary_enter(ey - kTabHeader, 2) : 0ull;
-#endif
   int bx[SLOTS], by[SLOTS];
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
@@ -461,9 +411,6 @@ __device__ double win_potential(const double* __restrict__ D, double* ey,
     }
   }
   tab_sync<GT>();
-#ifdef RHMC_TABLE_CANARY
-  if (GT) canary_leave(ey - kTabHeader, cv, 2);
-#endif
   return wave_sum_dpp(v);
 }
 
@@ -554,16 +501,14 @@ struct WinEG {
 // kernel from 100 to 200 stars).  Past 256 stars the state spills.
 struct WinGG {
   static __host__ __device__ size_t lds_bytes(int, int) { return kExpTab * sizeof(double); }
-  static __host__ __device__ size_t work_doubles(int K) {
-    return win_table_doubles(K) + kTabHeader;
-  }
+  static __host__ __device__ size_t work_doubles(int K) { return win_table_doubles(K); }
   using Ctx = WinG::Ctx;
   static __device__ __forceinline__ Ctx setup(double* lds, const double* D, int K, int rows,
                                               int cols, double* work) {
     exp_tab_fill(lds);
     __syncthreads();
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-    double* base = work + wave * (int64_t)work_doubles(K) + kTabHeader;
+    double* base = work + wave * (int64_t)work_doubles(K);
     Ctx g;
     g.etab = lds;
     g.tab = WinTables{base, base + K * kTabW};

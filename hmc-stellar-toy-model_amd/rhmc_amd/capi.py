@@ -39,8 +39,7 @@ OPT_PEAKS_FUSED = 5         # find_peaks: one-launch descent kernel where it exi
 OPT_DT_LANES = 6            # dt_trials: lanes per task (0: the library's choice, 64, 256)
 DT_GRAD_REFERENCE = 0       # rhmc_dt_opts.grad (RHMC_DT_GRAD_*, include/rhmc.h)
 DT_GRAD_FULL = 1
-(TABLES_STREAM, TABLES_STREAM_POISON, TABLES_POOL, TABLES_POOL_POISON, TABLES_POOL_KEEP,
- TABLES_POOL_SYNCFREE, TABLES_POOL_BARRIER) = range(7)
+TABLES_STREAM, TABLES_STREAM_POISON = 0, 1
 # RHMC_KERNEL_* values by name
 KERNELS = {"auto": 0, "generic": 1, "windowed": 2, "regwin": 3, "regwin32": 4,
            "regwin_f64": 5, "lane1": 6, "lane4": 7, "lane1_f64": 8, "pixmajor": 9,

@@ -204,11 +204,7 @@ typedef struct rhmc_ctx rhmc_ctx;
  *   buffer; STREAM_POISON = the same, filled with 0xFF bytes (NaN) before
  *   every launch, so that a read of an entry the launch did not write would
  *   show as a NaN result (tests/test_gpu_tables_determinism.py: none does).
- *   The POOL* values (a stream-ordered pool allocation per launch, round 5's
- *   first scheme, and its variants) reproduce a defect outside the kernels
- *   (a reused pool block is zeroed while the launch that
- *   received it runs); only -DRHMC_TABLE_DIAG builds accept them, the library
- *   returns RHMC_ERR_UNSUPPORTED.
+ *   Any other value is refused with RHMC_ERR_ARG.
  * RHMC_OPT_PEAKS_FUSED: 1 (default) = rhmc_find_peaks runs the one-launch
  *   descent kernel where it exists (32/48/64-px images, a PSF narrow enough
  *   for the 28-px window, no forced per-wave family), 0 = always the stepwise
@@ -226,12 +222,7 @@ enum {
 };
 enum {
   RHMC_TABLES_STREAM = 0,
-  RHMC_TABLES_STREAM_POISON = 1,
-  RHMC_TABLES_POOL = 2,
-  RHMC_TABLES_POOL_POISON = 3,
-  RHMC_TABLES_POOL_KEEP = 4,
-  RHMC_TABLES_POOL_SYNCFREE = 5,
-  RHMC_TABLES_POOL_BARRIER = 6
+  RHMC_TABLES_STREAM_POISON = 1
 };
 enum {
   RHMC_KERNEL_AUTO = 0,

@@ -13,7 +13,6 @@
 #   scripts/evidence.sh OUT trace NAME       rocprofv3 --kernel-trace --stats of
 #                                            one bench line (RJ lines add
 #                                            --memory-copy-trace)
-#   scripts/evidence.sh OUT det              WinGG table modes (det_tables.sh)
 # OUT is a directory under gpurun_out/.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
@@ -94,8 +93,6 @@ case $CMD in
     timeout -k 10 400 rocprofv3 --kernel-trace $extra --stats -d "$O/trace_$n" -o run \
       --output-format csv -- python3 bench.py ${LINE[$n]} > "$O/trace_$n.log" 2>&1 || exit 1
     tail -1 "$O/trace_$n.log" | cut -c1-200 ;;
-  det)
-    bash scripts/det_tables.sh "$O" ;;
   *) echo "unknown command $CMD"; exit 2 ;;
 esac
 echo "evidence $CMD done"

@@ -39,21 +39,6 @@ struct MhK1Args {
   Consts c;
 };
 
-// Workgroup prologue of the one-star register-window kernels: the image into
-// LDS (row pitch TL::P) and the exp table.
-template <class TL, typename DT>
-__device__ __forceinline__ DT* k1_stage_image(double* lds, const DT* gimg) {
-  constexpr int IMG = TL::P - 1;
-  DT* simg = reinterpret_cast<DT*>(lds + kExpTab);
-  for (int e = threadIdx.x; e < IMG * IMG; e += blockDim.x) {
-    const int r = e / IMG, cc = e - (e / IMG) * IMG;
-    simg[r * TL::P + cc] = gimg[e];
-  }
-  exp_tab_fill(lds);
-  __syncthreads();
-  return simg;
-}
-
 // sum over the image of B - D ln B = IMG^2 B - ln B sum D (the V of a
 // star-free image; the window sum corrects it), lnB = log_pos(B).  Wave-wide.
 template <class TL, typename DT>
@@ -208,18 +193,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
 energy_k1_tiledr(EnergyK1Args a) {
   using TL = TiledR<IMG, 28, DT>;
   extern __shared__ double lds[];
-  const DT* gimg;
-  if constexpr (sizeof(DT) == sizeof(float)) gimg = reinterpret_cast<const DT*>(a.Df);
-  else gimg = reinterpret_cast<const DT*>(a.D);
-  const DT* simg = k1_stage_image<TL>(lds, gimg);
+  const DT* simg = k1_stage_image<TL>(lds, k1_image<DT>(a));
   const Consts& c = a.c;
-  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-  if (TL::CPW * wave >= a.n) return;
-  const int lane = lane_id();
-  const int64_t ch = TL::CPW * wave + lane / TL::LPC;
-  const bool real = ch < a.n;                      // ragged tail: mirror the wave's first chain
-  const int64_t chr = real ? ch : TL::CPW * wave;
-  const bool writer = real && (lane % TL::LPC) == 0;
+  const K1Chain<TL::LPC> kc(a.n);
+  if (kc.none) return;
+  const int64_t ch = kc.chain, chr = kc.row;
+  const bool writer = kc.writer;
   const double f = a.q[3 * chr], x = a.q[3 * chr + 1], y = a.q[3 * chr + 2];
   if (a.T) {  // T(p, H(q)) (:353-363), the energy kernel's expression
     const double pf = a.p[3 * chr], px = a.p[3 * chr + 1], py = a.p[3 * chr + 2];

@@ -127,18 +127,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
 peaks_k1_tiledr(PeaksArgs a) {
   using TL = TiledR<IMG, 28, DT>;
   extern __shared__ double lds[];
-  const DT* gimg;
-  if constexpr (sizeof(DT) == sizeof(float)) gimg = reinterpret_cast<const DT*>(a.Df);
-  else gimg = reinterpret_cast<const DT*>(a.D);
-  const DT* simg = k1_stage_image<TL>(lds, gimg);
+  const DT* simg = k1_stage_image<TL>(lds, k1_image<DT>(a));
   const Consts& c = a.c;
-  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-  if (TL::CPW * wave >= a.n) return;
-  const int lane = lane_id();
-  const int64_t ch = TL::CPW * wave + lane / TL::LPC;
-  const bool real = ch < a.n;                      // ragged tail: mirror the wave's first seed
-  const int64_t chr = real ? ch : TL::CPW * wave;
-  const bool writer = real && (lane % TL::LPC) == 0;
+  const K1Chain<TL::LPC> kc(a.n);
+  if (kc.none) return;
+  const int64_t ch = kc.chain, chr = kc.row;
+  const bool writer = kc.writer;
 
   const double lnB = log_pos(c.B);
   const double sum_B = k1_background_V<TL>(simg, c.B, lnB);

@@ -790,20 +790,11 @@ __global__ void __launch_bounds__(256) integrate_win_kernel(LeapArgs a, int f_po
   win_store<SLOTS>(a, chain, chain, 3 * (int64_t)K, K, s, 0, 0, st);
 }
 
-// samplers.lightsource_gym.HMC_random's trajectory (samplers.py:519-552):
-// unit-mass leapfrog with a per-coordinate step vector dt[3K] and a per-chain
-// trajectory length steps[chain] >= 1, flux wall at c.f_lim with the
-// reference's quirks kept: the flip mask `iflip` is never cleared within a
-// trajectory (a star once below the wall has its flux momentum flipped on
-// every later step in which ANY star is below it, :529-541), and when the
-// last step flipped, p_tmp keeps the momentum the trajectory started from
-// (:547-550 update p_half, not p_tmp) — status bit RHMC_STATUS_REFLECT_F
-// marks those chains.  One wave per chain, star 64 s + lane in slot s.
-// DIAG: RHMC_random_diag's trajectory instead (samplers.py:766-800; dtv
-// unused): the one step dg.dt, the drift divided by the mass matrix at the
-// flux before it, dlnDetdq + dpMpdq in the flux force (diag_force_f, with the
-// start momentum, which s.pf, s.px, s.py keep for the REFLECT_F return
-// anyway), the same wall quirks, and q after every step to dg.trace.
+// samplers.lightsource_gym.HMC_random's trajectory (samplers.py:519-552), or
+// with DIAG RHMC_random_diag's (:766-800): random_trajectory (rhmc_traj.hpp,
+// the rule and the reference's wall quirks) on the slotted gradient.  One wave
+// per chain, star 64 t + lane in slot t; the steps dtv[3K] sit in registers,
+// and s.p* keep the start momentum for the DIAG force and the REFLECT_F return.
 template <class G, int SLOTS, bool DIAG>
 __device__ __forceinline__ void hmc_random_win_body(double* lds, const LeapArgs& a,
                                                     const double* __restrict__ dtv,
@@ -819,91 +810,54 @@ __device__ __forceinline__ void hmc_random_win_body(double* lds, const LeapArgs&
   const int lane = lane_id();
   WinState<SLOTS> s;
   win_load<SLOTS>(a, chain, 3 * (int64_t)K, K, s);
-  double dtf[SLOTS], dtx[SLOTS], dty[SLOTS];
+  double dtr[SLOTS][3];
+  if constexpr (!DIAG) {
+#pragma unroll
+    for (int t = 0; t < SLOTS; ++t) {
+      const int ks = s.own[t] ? kWave * t + lane : 0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dtr[t][j] = dtv[3 * ks + j];
+    }
+  }
+  double hf[SLOTS], hx[SLOTS], hy[SLOTS];
 #pragma unroll
   for (int t = 0; t < SLOTS; ++t) {
-    if constexpr (DIAG) {
-      dtf[t] = dtx[t] = dty[t] = dg.dt;
-    } else {
-      const int ks = s.own[t] ? kWave * t + lane : 0;
-      dtf[t] = dtv[3 * ks];
-      dtx[t] = dtv[3 * ks + 1];
-      dty[t] = dtv[3 * ks + 2];
-    }
+    hf[t] = s.pf[t];
+    hx[t] = s.px[t];
+    hy[t] = s.py[t];
   }
-  double gf[SLOTS], gx[SLOTS], gy[SLOTS];
-  auto force = [&]() {  // DIAG: dVdq + dlnDetdq + dpMpdq (:766)
-    if constexpr (DIAG) {
+  const bool flip = random_trajectory<SLOTS, DIAG>(
+      s.f, s.x, s.y, hf, hx, hy, steps[chain], c.f_lim, dg,
+      [&](int t, int j) RHMC_INLINE_LAMBDA { return dtr[t][j]; },
+      [&](int t) RHMC_INLINE_LAMBDA { return s.own[t]; },
+      [&](bool b) RHMC_INLINE_LAMBDA { return __builtin_amdgcn_ballot_w64(b) != 0; },
+      [&](double (&gf)[SLOTS], double (&gx)[SLOTS], double (&gy)[SLOTS]) RHMC_INLINE_LAMBDA {
+        G::template gradient<SLOTS>(gctx, K, s.f, s.x, s.y, c, lc, false, gf, gx, gy);
+      },
+      [&](int t, double& sf, double& sxy) RHMC_INLINE_LAMBDA {
+        sf = s.pf[t] * s.pf[t];
+        sxy = s.px[t] * s.px[t] + s.py[t] * s.py[t];
+      },
+      [&](int row) RHMC_INLINE_LAMBDA {
+        if (!dg.trace || row >= dg.rows) return;
 #pragma unroll
-      for (int t = 0; t < SLOTS; ++t)
-        gf[t] = diag_force_f(gf[t], s.f[t], s.pf[t] * s.pf[t],
-                             s.px[t] * s.px[t] + s.py[t] * s.py[t], dg.inv_f1);
-    }
-  };
-  auto trace = [&](int row) {  // DIAG: q to row `row` of the chain's trace
-    if constexpr (DIAG) {
-      if (!dg.trace || row >= dg.rows) return;
-#pragma unroll
-      for (int t = 0; t < SLOTS; ++t) {
-        if (!s.own[t]) continue;
-        double* r = dg.trace + (chain * dg.rows + row) * 3 * K + 3 * (kWave * t + lane);
-        r[0] = s.f[t];
-        r[1] = s.x[t];
-        r[2] = s.y[t];
-      }
-    }
-  };
-  trace(0);
-  G::template gradient<SLOTS>(gctx, K, s.f, s.x, s.y, c, lc, false, gf, gx, gy);
-  force();
-  double hf[SLOTS], hx[SLOTS], hy[SLOTS];
-  bool iflip[SLOTS];
-#pragma unroll
-  for (int t = 0; t < SLOTS; ++t) {  // :519
-    hf[t] = s.pf[t] - dtf[t] * gf[t] / 2.0;
-    hx[t] = s.px[t] - dtx[t] * gx[t] / 2.0;
-    hy[t] = s.py[t] - dty[t] * gy[t] / 2.0;
-    iflip[t] = false;
-  }
-  bool flip = false;
-  const int n = steps[chain];
-  for (int i = 0; i < n; ++i) {
-    bool below_any = false;
-#pragma unroll
-    for (int t = 0; t < SLOTS; ++t) {
-      if constexpr (DIAG) {                                             // :770-771
-        diag_drift(s.f[t], s.x[t], s.y[t], hf[t], hx[t], hy[t], dg.dt, dg.inv_f1);
-      } else {
-        s.f[t] = s.f[t] + dtf[t] * hf[t];                               // :523
-        s.x[t] = s.x[t] + dtx[t] * hx[t];
-        s.y[t] = s.y[t] + dty[t] * hy[t];
-      }
-      const bool below = s.own[t] && s.f[t] < c.f_lim;                  // :526-529
-      iflip[t] = iflip[t] || below;
-      below_any = below_any || below;
-    }
-    flip = __builtin_amdgcn_ballot_w64(below_any) != 0;
-    trace(i + 1);
-    G::template gradient<SLOTS>(gctx, K, s.f, s.x, s.y, c, lc, false, gf, gx, gy);
-    force();
-#pragma unroll
-    for (int t = 0; t < SLOTS; ++t) {
-      const double kept = -hf[t];                                       // :531
-      hf[t] = hf[t] - dtf[t] * gf[t];                                   // :532, :535
-      hx[t] = hx[t] - dtx[t] * gx[t];
-      hy[t] = hy[t] - dty[t] * gy[t];
-      if (flip && iflip[t]) hf[t] = kept;                               // :533
-    }
-  }
+        for (int t = 0; t < SLOTS; ++t) {
+          if (!s.own[t]) continue;
+          double* r = dg.trace + (chain * dg.rows + row) * 3 * K + 3 * (kWave * t + lane);
+          r[0] = s.f[t];
+          r[1] = s.x[t];
+          r[2] = s.y[t];
+        }
+      });
   unsigned st = 0u;
   if (flip) {
-    st |= RHMC_STATUS_REFLECT_F;  // p_tmp stays the starting momentum (:547-550)
-  } else {                        // :551-552, dVdq at the same q as the last step
+    st |= RHMC_STATUS_REFLECT_F;  // s.p* stay the starting momentum
+  } else {
 #pragma unroll
     for (int t = 0; t < SLOTS; ++t) {
-      s.pf[t] = hf[t] + dtf[t] * gf[t] / 2.0;
-      s.px[t] = hx[t] + dtx[t] * gx[t] / 2.0;
-      s.py[t] = hy[t] + dty[t] * gy[t] / 2.0;
+      s.pf[t] = hf[t];
+      s.px[t] = hx[t];
+      s.py[t] = hy[t];
     }
   }
   win_store<SLOTS>(a, chain, chain, 3 * (int64_t)K, K, s, 0, 0, st);

@@ -387,9 +387,9 @@ leapfrog_pk(LeapArgsKR a, int f_pos) {
     double* tr = nullptr;  // the chain's trace rows (a mirrored tail chain writes none)
     if constexpr (DG)
       if (a.diag.trace && real) tr = a.diag.trace + chain * a.diag.rows * 3 * K;
-    if (km_hmc_random_steps<1, decltype(grad), true, DG>(f, x, y, pf, px, py, own, tab,
-                                                         a.steps[chain_r], a.dtv, c, grad,
-                                                         a.diag, tr, K, a.p + cbase)) {
+    if (km_trajectory<1, decltype(grad), true, DG>(f, x, y, pf, px, py, own, tab,
+                                                   a.steps[chain_r], a.dtv, c, grad, a.diag, tr,
+                                                   K, a.p + cbase)) {
       st |= RHMC_STATUS_REFLECT_F;  // p_tmp stays the starting momentum (:547-550)
       pf[0] = own[0] ? a.p[e] : 0.0;
       px[0] = own[0] ? a.p[e + 1] : 0.0;

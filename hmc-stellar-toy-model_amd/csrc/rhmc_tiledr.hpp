@@ -391,11 +391,59 @@ struct TiledR {
   }
 };
 
+// ---- the frame of the one-star kernels --------------------------------------
+// The image a kernel caches as DT: Df (every pixel exact in fp32) or D.
+template <typename DT, class ARGS>
+__device__ __forceinline__ const DT* k1_image(const ARGS& a) {
+  if constexpr (sizeof(DT) == sizeof(float)) return reinterpret_cast<const DT*>(a.Df);
+  else return reinterpret_cast<const DT*>(a.D);
+}
+
+// Workgroup prologue of the register-window kernels: the image into LDS (row
+// pitch TL::P) and the exp table.
+template <class TL, typename DT>
+__device__ __forceinline__ DT* k1_stage_image(double* lds, const DT* gimg) {
+  constexpr int IMG = TL::P - 1;
+  DT* simg = reinterpret_cast<DT*>(lds + kExpTab);
+  for (int e = threadIdx.x; e < IMG * IMG; e += blockDim.x) {
+    const int r = e / IMG, cc = e - (e / IMG) * IMG;
+    simg[r * TL::P + cc] = gimg[e];
+  }
+  exp_tab_fill(lds);
+  __syncthreads();
+  return simg;
+}
+
+// Wave to chain with LPC lanes per chain: the lane's chain, the chain whose
+// state it reads (`row`: a chain past the end mirrors the wave's first one,
+// so a ragged last wave computes on real data) and the one lane that writes.
+// For the kernels without a step loop at the register limit (energy, peaks):
+// in the step kernels below the struct's values held across the loop cost a
+// block of register copies per step (measured: 12 % of the DIAG trajectory's
+// rate), so those spell the mapping and their epilogue out.
+template <int LPC>
+struct K1Chain {
+  int64_t chain, row;
+  bool none, real, writer;  // none: the whole wave is past the end
+  __device__ __forceinline__ explicit K1Chain(int64_t n_chains) {
+    constexpr int CPW = kWave / LPC;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
+    const int lane = lane_id();
+    none = CPW * wave >= n_chains;
+    chain = CPW * wave + lane / LPC;
+    real = chain < n_chains;
+    row = real ? chain : CPW * wave;
+    writer = real && (lane % LPC) == 0;
+  }
+};
+
 // One wave = 4 chains x 16 lanes; W waves per workgroup share the LDS image.
 template <int IMG, int WIN, typename DT, bool PROF = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
 leapfrog_k1_tiledr(LeapArgsK1 a) {
   using TL = TiledR<IMG, WIN, DT>;
+  // (this kernel keeps its staging spelled out too: through k1_stage_image
+  // the staging loop unrolls differently in some instantiations)
   extern __shared__ double lds[];
   DT* simg = reinterpret_cast<DT*>(lds + kExpTab);
   const DT* gimg;
@@ -473,18 +521,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
 integrate_k1_tiledr(LeapArgsK1 a, int f_pos) {
   using TL = TiledR<IMG, WIN, DT>;
   extern __shared__ double lds[];
-  DT* simg = reinterpret_cast<DT*>(lds + kExpTab);
-  const DT* gimg;
-  if constexpr (sizeof(DT) == sizeof(float)) gimg = reinterpret_cast<const DT*>(a.Df);
-  else gimg = reinterpret_cast<const DT*>(a.D);
+  const DT* simg = k1_stage_image<TL>(lds, k1_image<DT>(a));
   const Consts& c = a.c;
   const int W = blockDim.x / kWave;
-  for (int e = threadIdx.x; e < IMG * IMG; e += blockDim.x) {
-    const int r = e / IMG, cc = e - (e / IMG) * IMG;
-    simg[r * TL::P + cc] = gimg[e];
-  }
-  exp_tab_fill(lds);
-  __syncthreads();
   const int64_t wave = (int64_t)blockIdx.x * W + (threadIdx.x / kWave);
   if (TL::CPW * wave >= a.n_chains) return;
   const int lane = lane_id();
@@ -574,36 +613,22 @@ integrate_k1_tiledr(LeapArgsK1 a, int f_pos) {
   }
 }
 
-// samplers.lightsource_gym.HMC_random's trajectory (samplers.py:519-552) for one
-// star on the register-window gradient: unit-mass leapfrog with the step vector
-// dtv[3], the chain's length steps[chain] >= 1 (wave lanes of finished chains
-// idle; every cross-lane exchange stays inside a chain's 16 lanes), the flux wall
-// at c.f_lim with the reference's quirks (hmc_random_win_kernel: the flip mask
-// is never cleared; a trajectory whose last step flipped keeps its starting
-// momentum, status RHMC_STATUS_REFLECT_F).  dVdq without the metric (:365-425).
-// DIAG: RHMC_random_diag's trajectory instead (samplers.py:766-800; dtv
-// unused): the one step dg.dt, the drift divided by the mass matrix at the
-// flux before it, dlnDetdq + dpMpdq in the flux force (diag_force_f, with the
-// start momentum, which pf, px, py keep for the REFLECT_F return anyway), the
-// same wall quirks, and q after every step to dg.trace when asked for.
+// samplers.lightsource_gym.HMC_random's trajectory (samplers.py:519-552), or
+// with DIAG RHMC_random_diag's (:766-800), for one star on the register-window
+// gradient: random_trajectory (rhmc_traj.hpp, the rule and the reference's
+// wall quirks) with one slot.  The step vector dtv[3] sits in registers; wave
+// lanes of finished chains idle, and every cross-lane exchange stays inside a
+// chain's 16 lanes; pf, px, py keep the start momentum for the DIAG force and
+// the REFLECT_F return.
 template <int IMG, typename DT, bool DIAG>
 __device__ __forceinline__ void hmc_random_k1_body(double* lds, const LeapArgsK1& a,
                                                    const double* __restrict__ dtv,
                                                    const int32_t* __restrict__ steps,
                                                    const DiagArgs& dg) {
   using TL = TiledR<IMG, 28, DT>;
-  DT* simg = reinterpret_cast<DT*>(lds + kExpTab);
-  const DT* gimg;
-  if constexpr (sizeof(DT) == sizeof(float)) gimg = reinterpret_cast<const DT*>(a.Df);
-  else gimg = reinterpret_cast<const DT*>(a.D);
+  const DT* simg = k1_stage_image<TL>(lds, k1_image<DT>(a));
   const Consts& c = a.c;
   const int W = blockDim.x / kWave;
-  for (int e = threadIdx.x; e < IMG * IMG; e += blockDim.x) {
-    const int r = e / IMG, cc = e - (e / IMG) * IMG;
-    simg[r * TL::P + cc] = gimg[e];
-  }
-  exp_tab_fill(lds);
-  __syncthreads();
   const int64_t wave = (int64_t)blockIdx.x * W + (threadIdx.x / kWave);
   if (TL::CPW * wave >= a.n_chains) return;
   const int lane = lane_id();
@@ -611,76 +636,48 @@ __device__ __forceinline__ void hmc_random_k1_body(double* lds, const LeapArgsK1
   const bool real = chain < a.n_chains;            // ragged tail: mirror the wave's first chain
   const int64_t cr = real ? chain : TL::CPW * wave;
   const int64_t base = cr * 3;
-  double f = a.q[base], x = a.q[base + 1], y = a.q[base + 2];
-  double pf = a.p[base], px = a.p[base + 1], py = a.p[base + 2];
-  double dtf, dtx, dty;
-  if constexpr (DIAG) {
-    dtf = dtx = dty = dg.dt;
-  } else {
-    dtf = dtv[0], dtx = dtv[1], dty = dtv[2];
-  }
+  double f[1] = {a.q[base]}, x[1] = {a.q[base + 1]}, y[1] = {a.q[base + 2]};
+  const double pf = a.p[base], px = a.p[base + 1], py = a.p[base + 2];
+  double dtr[3];
+  if constexpr (!DIAG) dtr[0] = dtv[0], dtr[1] = dtv[1], dtr[2] = dtv[2];
   const LeanConsts lc = lean_consts(c);
   typename TL::Cache cache;
   TL::init(cache);
-  double gf, gx, gy;
-  auto grad = [&]() {                              // dVdq (:365-425)
-    TL::gradient(lds, simg, cache, f, x, y, c, lc, gf, gx, gy);
-    if (c.use_prior) gf += c.alpha / f;            // :408-409
-    if constexpr (DIAG) gf = diag_force_f(gf, f, pf * pf, px * px + py * py, dg.inv_f1);
-  };
-  // DIAG: row t of the chain's trace, written by the chain's first lane
-  auto trace = [&](int t) {
-    if constexpr (DIAG) {
-      if (dg.trace && (lane % TL::LPC) == 0 && real && t < dg.rows) {
-        double* r = dg.trace + (chain * dg.rows + t) * 3;
-        r[0] = f;
-        r[1] = x;
-        r[2] = y;
-      }
-    }
-  };
-  trace(0);
-  grad();
-  double hf = pf - dtf * gf / 2.0, hx = px - dtx * gx / 2.0,  // :519
-         hy = py - dty * gy / 2.0;
-  bool iflip = false, flip = false;
-  const int n = steps[cr];
-  for (int t = 0; t < n; ++t) {
-    if constexpr (DIAG) {
-      diag_drift(f, x, y, hf, hx, hy, dtf, dg.inv_f1);         // :770-771
-      trace(t + 1);
-    } else {
-      f = f + dtf * hf;                                        // :523
-      x = x + dtx * hx;
-      y = y + dty * hy;
-    }
-    flip = f < c.f_lim;                                        // :526-529 (one star)
-    iflip = iflip || flip;
-    grad();
-    const double kept = -hf;                                   // :531
-    hf = hf - dtf * gf;                                        // :532, :535
-    hx = hx - dtx * gx;
-    hy = hy - dty * gy;
-    if (flip && iflip) hf = kept;                              // :533
-  }
+  double hf[1] = {pf}, hx[1] = {px}, hy[1] = {py};
+  const bool flip = random_trajectory<1, DIAG>(
+      f, x, y, hf, hx, hy, steps[cr], c.f_lim, dg,
+      [&](int, int j) RHMC_INLINE_LAMBDA { return dtr[j]; },
+      [](int) RHMC_INLINE_LAMBDA { return true; },
+      [](bool b) RHMC_INLINE_LAMBDA { return b; },
+      [&](double (&gf)[1], double (&gx)[1], double (&gy)[1]) RHMC_INLINE_LAMBDA {  // dVdq (:365-425)
+        TL::gradient(lds, simg, cache, f[0], x[0], y[0], c, lc, gf[0], gx[0], gy[0]);
+        if (c.use_prior) gf[0] += c.alpha / f[0];  // :408-409
+      },
+      [&](int, double& sf, double& sxy) RHMC_INLINE_LAMBDA {
+        sf = pf * pf;
+        sxy = px * px + py * py;
+      },
+      [&](int row) RHMC_INLINE_LAMBDA {
+        if (dg.trace && (lane % TL::LPC) == 0 && real && row < dg.rows) {
+          double* r = dg.trace + (chain * dg.rows + row) * 3;
+          r[0] = f[0];
+          r[1] = x[0];
+          r[2] = y[0];
+        }
+      });
   unsigned st = 0u;
-  if (flip) {
-    st |= RHMC_STATUS_REFLECT_F;  // p_tmp stays the starting momentum (:547-550)
-  } else {                        // :551-552, dVdq at the same q as the last step
-    pf = hf + dtf * gf / 2.0;
-    px = hx + dtx * gx / 2.0;
-    py = hy + dty * gy / 2.0;
-  }
+  if (flip) st |= RHMC_STATUS_REFLECT_F;  // the starting momentum stays
   if ((lane % TL::LPC) == 0 && real) {
-    if (!(isfinite(f) && isfinite(x) && isfinite(y) && isfinite(pf) && isfinite(px) &&
-          isfinite(py)))
+    const double qf = flip ? pf : hf[0], qx = flip ? px : hx[0], qy = flip ? py : hy[0];
+    if (!(isfinite(f[0]) && isfinite(x[0]) && isfinite(y[0]) && isfinite(qf) && isfinite(qx) &&
+          isfinite(qy)))
       st |= RHMC_STATUS_NONFINITE;
-    a.q[base] = f;
-    a.q[base + 1] = x;
-    a.q[base + 2] = y;
-    a.p[base] = pf;
-    a.p[base + 1] = px;
-    a.p[base + 2] = py;
+    a.q[base] = f[0];
+    a.q[base + 1] = x[0];
+    a.q[base + 2] = y[0];
+    a.p[base] = qf;
+    a.p[base + 1] = qx;
+    a.p[base + 2] = qy;
     if (a.status) a.status[chain] = (int32_t)st;
   }
 }

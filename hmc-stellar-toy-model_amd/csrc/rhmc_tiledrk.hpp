@@ -736,150 +736,79 @@ __device__ __forceinline__ void km_explicit_steps(double (&f)[SLOTS], double (&x
   }
 }
 
-// samplers.lightsource_gym.HMC_random's trajectory (samplers.py:519-552) for the
-// chain's stars: unit mass, per-coordinate steps dtv, n leapfrog steps, the
-// flux wall at c.f_lim with the reference's quirks (hmc_random_win_kernel: a
-// star's flip flag is never cleared; the flip applies on every step where ANY
-// of the chain's stars is below the wall).  p holds the half-step momentum;
-// returns true when the last step flipped — the caller then keeps the
-// starting momentum (:547-550).  dVdq without the metric (:365-425).
-// DIAG: RHMC_random_diag's trajectory instead (samplers.py:766-800; dtv
-// unused): the one step dg.dt, the drift divided by the mass matrix at the
-// flux before it, dlnDetdq + dpMpdq in the flux force (diag_force_f) from the
-// start momentum's pf^2 and px^2 + py^2, which are kept per star (p itself
-// becomes the half-step momentum), the same wall quirks, and q after every
-// step to the chain's trace rows tr [dg.rows][3K] (null: none).  The
-// pixel-major kernel (RELOAD) has no registers left for those two values (it
-// spilled): it re-reads the start momentum from p0, the chain's row of p,
-// which nothing writes before the epilogue, where the force needs it, the way
-// the steps dtv are re-read.
+// samplers.lightsource_gym.HMC_random's trajectory (samplers.py:519-552), or
+// with DIAG RHMC_random_diag's (:766-800), for the chain's stars (lane m:
+// stars m + 32 t): random_trajectory (rhmc_traj.hpp, the rule and the
+// reference's wall quirks) with what the two register kernels do their own
+// way.  The steps dtv are re-read from memory (L1/L2) where used instead of
+// being held in registers across the gradient (register pressure at two
+// slots; the index goes through an empty asm so that the loads are not
+// hoisted).  The state goes to the star table before every gradient and, under
+// RELOAD, comes back from it after.  p becomes the half-step momentum, so the
+// squares of the start momentum that the DIAG force needs are kept per star;
+// the pixel-major kernel (RELOAD) has no registers left for those two values
+// (it spilled) and re-reads the start momentum from p0, the chain's row of p,
+// which nothing writes before the epilogue.  DIAG: q after every step to the
+// chain's trace rows tr [dg.rows][3K] (null: none).  Returns true when the
+// last step flipped: the caller then re-reads the start momentum.
 template <int SLOTS, class GRAD, bool RELOAD = false, bool DIAG = false>
-__device__ __forceinline__ bool km_hmc_random_steps(double (&f)[SLOTS], double (&x)[SLOTS],
-                                                    double (&y)[SLOTS], double (&pf)[SLOTS],
-                                                    double (&px)[SLOTS], double (&py)[SLOTS],
-                                                    const bool (&own)[SLOTS], KRStar* tab,
-                                                    int n, const double* __restrict__ dtv,
-                                                    const Consts& c, GRAD grad,
-                                                    const DiagArgs& dg = DiagArgs{},
-                                                    double* tr = nullptr, int K = 0,
-                                                    const double* __restrict__ p0 = nullptr) {
+__device__ __forceinline__ bool km_trajectory(double (&f)[SLOTS], double (&x)[SLOTS],
+                                              double (&y)[SLOTS], double (&pf)[SLOTS],
+                                              double (&px)[SLOTS], double (&py)[SLOTS],
+                                              const bool (&own)[SLOTS], KRStar* tab, int n,
+                                              const double* __restrict__ dtv, const Consts& c,
+                                              GRAD grad, const DiagArgs& dg = DiagArgs{},
+                                              double* tr = nullptr, int K = 0,
+                                              const double* __restrict__ p0 = nullptr) {
   const int m = lane_id() & 31;
-  // the steps are re-read from memory (L1/L2) where used instead of being held
-  // in registers across the gradient (register pressure at two slots)
-  // (the index goes through an empty asm so that the loads are not hoisted)
-  auto dti = [&](int t, int j) {
-    if constexpr (DIAG) {
-      return dg.dt;
-    } else {
-      int i = 3 * (own[t] ? 32 * t + m : 0) + j;
-      asm volatile("" : "+v"(i));
-      return dtv[i];
-    }
+  auto fresh = [&](int t, int j) RHMC_INLINE_LAMBDA {  // element j of star t's row of three
+    int i = 3 * (own[t] ? 32 * t + m : 0) + j;
+    asm volatile("" : "+v"(i));
+    return i;
   };
   double sf[SLOTS], sxy[SLOTS];
-  auto trace = [&](int row) {
-    if constexpr (DIAG) {
-      if (!tr || row >= dg.rows) return;
-#pragma unroll
-      for (int t = 0; t < SLOTS; ++t) {
-        if (!own[t]) continue;
-        double* r = tr + (int64_t)row * 3 * K + 3 * (32 * t + m);
-        r[0] = f[t];
-        r[1] = x[t];
-        r[2] = y[t];
-      }
-    }
-  };
-  if constexpr (DIAG) {
-    if constexpr (!RELOAD) {
-#pragma unroll
-      for (int t = 0; t < SLOTS; ++t) {
-        sf[t] = pf[t] * pf[t];
-        sxy[t] = px[t] * px[t] + py[t] * py[t];
-      }
-    }
-    trace(0);
-  }
-  auto start_sq = [&](int t, double& s_f, double& s_xy) {
-    if constexpr (RELOAD) {
-      int i = 3 * (own[t] ? 32 * t + m : 0);
-      asm volatile("" : "+v"(i));
-      const double u = p0[i], v = p0[i + 1], w = p0[i + 2];
-      s_f = u * u;
-      s_xy = v * v + w * w;
-    } else {
-      s_f = sf[t];
-      s_xy = sxy[t];
-    }
-  };
-  auto dtf = [&](int t) { return dti(t, 0); };
-  auto dtx = [&](int t) { return dti(t, 1); };
-  auto dty = [&](int t) { return dti(t, 2); };
-  bool iflip[SLOTS];
-#pragma unroll
-  for (int t = 0; t < SLOTS; ++t) iflip[t] = false;
-  double gf[SLOTS], gx[SLOTS], gy[SLOTS];
-  auto gradient = [&]() {
-    grad(x, y, gf, gx, gy);
-    if constexpr (RELOAD) kr_reload<SLOTS>(tab, f, x, y, own);
-#pragma unroll
-    for (int t = 0; t < SLOTS; ++t)
-      if (c.use_prior) gf[t] += c.alpha / f[t];    // :408-409
-    if constexpr (DIAG) {
-#pragma unroll
-      for (int t = 0; t < SLOTS; ++t) {
-        double s_f, s_xy;
-        start_sq(t, s_f, s_xy);
-        gf[t] = diag_force_f(gf[t], f[t], s_f, s_xy, dg.inv_f1);
-      }
-    }
-  };
-  kr_publish<SLOTS>(tab, f, x, y, own);
-  gradient();
-#pragma unroll
-  for (int t = 0; t < SLOTS; ++t) {                // :519
-    pf[t] = pf[t] - dtf(t) * gf[t] / 2.0;
-    px[t] = px[t] - dtx(t) * gx[t] / 2.0;
-    py[t] = py[t] - dty(t) * gy[t] / 2.0;
-  }
-  bool flip = false;
-  for (int s = 0; s < n; ++s) {
-    bool below_any = false;
+  if constexpr (DIAG && !RELOAD) {
 #pragma unroll
     for (int t = 0; t < SLOTS; ++t) {
-      if constexpr (DIAG) {                        // :770-771
-        diag_drift(f[t], x[t], y[t], pf[t], px[t], py[t], dg.dt, dg.inv_f1);
-      } else {
-        f[t] = f[t] + dtf(t) * pf[t];              // :523
-        x[t] = x[t] + dtx(t) * px[t];
-        y[t] = y[t] + dty(t) * py[t];
-      }
-      const bool below = own[t] && f[t] < c.f_lim; // :526-529
-      iflip[t] = iflip[t] || below;
-      below_any = below_any || below;
-    }
-    flip = half_any(below_any);
-    trace(s + 1);
-    kr_publish<SLOTS>(tab, f, x, y, own);
-    gradient();
-#pragma unroll
-    for (int t = 0; t < SLOTS; ++t) {
-      const double kept = -pf[t];                  // :531
-      pf[t] = pf[t] - dtf(t) * gf[t];              // :532, :535
-      px[t] = px[t] - dtx(t) * gx[t];
-      py[t] = py[t] - dty(t) * gy[t];
-      if (flip && iflip[t]) pf[t] = kept;          // :533
+      sf[t] = pf[t] * pf[t];
+      sxy[t] = px[t] * px[t] + py[t] * py[t];
     }
   }
-  if (!flip) {
+  return random_trajectory<SLOTS, DIAG>(
+      f, x, y, pf, px, py, n, c.f_lim, dg,
+      [&](int t, int j) RHMC_INLINE_LAMBDA { return dtv[fresh(t, j)]; },
+      [&](int t) RHMC_INLINE_LAMBDA { return own[t]; },
+      [&](bool b) RHMC_INLINE_LAMBDA { return half_any(b); },
+      [&](double (&gf)[SLOTS], double (&gx)[SLOTS], double (&gy)[SLOTS]) RHMC_INLINE_LAMBDA {
+        kr_publish<SLOTS>(tab, f, x, y, own);
+        grad(x, y, gf, gx, gy);
+        if constexpr (RELOAD) kr_reload<SLOTS>(tab, f, x, y, own);
 #pragma unroll
-    for (int t = 0; t < SLOTS; ++t) {              // :551-552
-      pf[t] = pf[t] + dtf(t) * gf[t] / 2.0;
-      px[t] = px[t] + dtx(t) * gx[t] / 2.0;
-      py[t] = py[t] + dty(t) * gy[t] / 2.0;
-    }
-  }
-  return flip;
+        for (int t = 0; t < SLOTS; ++t)
+          if (c.use_prior) gf[t] += c.alpha / f[t];  // :408-409
+      },
+      [&](int t, double& s_f, double& s_xy) RHMC_INLINE_LAMBDA {
+        if constexpr (RELOAD) {
+          const int i = fresh(t, 0);
+          const double u = p0[i], v = p0[i + 1], w = p0[i + 2];
+          s_f = u * u;
+          s_xy = v * v + w * w;
+        } else {
+          s_f = sf[t];
+          s_xy = sxy[t];
+        }
+      },
+      [&](int row) RHMC_INLINE_LAMBDA {
+        if (!tr || row >= dg.rows) return;
+#pragma unroll
+        for (int t = 0; t < SLOTS; ++t) {
+          if (!own[t]) continue;
+          double* r = tr + (int64_t)row * 3 * K + 3 * (32 * t + m);
+          r[0] = f[t];
+          r[1] = x[t];
+          r[2] = y[t];
+        }
+      });
 }
 
 // Two chains per wave (32 lanes each), W waves per workgroup; two waves per
@@ -975,7 +904,7 @@ leapfrog_kr(LeapArgsKR a, int f_pos) {
     double* tr = nullptr;  // the chain's trace rows (a mirrored tail chain writes none)
     if constexpr (DG)
       if (a.diag.trace && chain < a.n_chains) tr = a.diag.trace + chain * a.diag.rows * 3 * K;
-    if (km_hmc_random_steps<SLOTS, decltype(grad), false, DG>(
+    if (km_trajectory<SLOTS, decltype(grad), false, DG>(
             f, x, y, pf, px, py, own, tab, a.steps[chain_r], a.dtv, c, grad, a.diag, tr, K)) {
       st |= RHMC_STATUS_REFLECT_F;  // p_tmp stays the starting momentum (:547-550)
 #pragma unroll

@@ -404,3 +404,5 @@ __device__ __forceinline__ double half_sum_dpp(double v) {
 }
 
 }  // namespace rhmc
+
+#include "rhmc_traj.hpp"  // the HMC_random / RHMC_random_diag trajectory

@@ -1,0 +1,89 @@
+// traj_bodies.cpp — which kernel body serves a random-length trajectory
+// (rhmc_hmc_random, rhmc_diag_random).  Host-only, csrc/rhmc_select.hpp alone:
+// select(..., Op::HmcRandom, ...) gives the plan, and body_key() names the
+// instantiation that csrc/rhmc_launch.hpp's switches (launch_hmc_random_t,
+// launch_k1_w28, launch_multi, launch_kr, with_path) launch for it:
+//   regwin1/IMG/DT          (diag_)hmc_random_k1_tiledr<IMG, DT>
+//   pixmajor/IMG            leapfrog_pk<IMG, 10, SOLVER>
+//   multiwin/DT/SLOTS/TAB   leapfrog_kr<DT, SLOTS, TAB, SOLVER, 1>
+//   slotted/POLICY/SLOTS    (diag_)hmc_random_win_kernel<G, SLOTS>
+// Built and run by tests/test_traj_bodies.py.
+//   traj_bodies sweep                                  the distinct keys
+//   traj_bodies side K img_f32 kernel n_chains [...]   one key per group of five
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <set>
+#include <string>
+
+#include "rhmc_select.hpp"
+
+using namespace rhmc;
+
+// MI355X: 160 KB of LDS per workgroup, 256 compute units.
+static SelectIn image(int side, bool f32, int kernel) {
+  SelectIn s;
+  s.rows = s.cols = side;
+  s.img_f32 = f32;
+  s.max_lds = 160 * 1024;
+  s.n_cu = 256;
+  s.kernel = kernel;
+  return s;
+}
+
+static std::string body_key(const SelectIn& s, int K, int64_t n) {
+  const double sigma = 3.5 / 2.354;  // the reference PSF, FWHM 3.5 px
+  const Plan pl = select(s, /*use_Vc*/ false, 1.0 / (2.0 * sigma * sigma), Op::HmcRandom, K, n);
+  const std::string side = std::to_string(s.rows);
+  switch (pl.family) {
+    case Family::Unsupported: return "Unsupported";
+    case Family::RegWin1:  // launch_k1_w28: with_side3, the 28-px window
+      if (s.rows != 32 && s.rows != 48 && s.rows != 64) return "regwin1/no-such-side";
+      return "regwin1/" + side + (pl.f32 ? "/float" : "/double");
+    case Family::PixMajor:  // launch_multi: with_side2
+      if (s.rows != 32 && s.rows != 48) return "pixmajor/no-such-side";
+      return "pixmajor/" + side;
+    case Family::MultiWin: {  // launch_kr, one wave per chain pair
+      const char* dt = pl.f32 ? "float" : "double";
+      if (pl.split != 1) return "multiwin/split";
+      if (pl.tables) return std::string("multiwin/") + dt + "/1/tab";
+      return std::string("multiwin/") + dt + (pl.slots == 1 ? "/1/notab" : "/2/notab");
+    }
+    default: break;  // launch_hmc_random_t: everything else goes with_path
+  }
+  if (pl.path == 32 || pl.path == 48) {  // with_slots: 1, 2, else 4
+    const int sl = win_slots(K);
+    return "slotted/Dense" + std::to_string(pl.path) + "/" + std::to_string(sl <= 2 ? sl : 4);
+  }
+  if (K >= kWinGlobalFromK) {  // with_big
+    const int sl = K <= 128 ? 2 : K <= 256 ? 4 : K <= 512 ? 8 : 16;
+    return "slotted/WinGG/" + std::to_string(sl);
+  }
+  return "slotted/WinG/1";
+}
+
+int main(int argc, char** argv) {
+  if (argc == 2 && !std::strcmp(argv[1], "sweep")) {
+    std::set<std::string> keys;
+    for (int side : {32, 48, 64, 96})
+      for (int K = 1; K <= kMaxK; ++K)
+        for (int f32 = 0; f32 < 2; ++f32)
+          for (int kernel = RHMC_KERNEL_AUTO; kernel <= RHMC_KERNEL_DENSE; ++kernel)
+            for (int64_t n : {(int64_t)4, (int64_t)65536})
+              keys.insert(body_key(image(side, f32 != 0, kernel), K, n));
+    for (const std::string& k : keys) std::puts(k.c_str());
+    return 0;
+  }
+  if (argc < 6 || (argc - 1) % 5 != 0) {
+    std::fprintf(stderr, "usage: %s sweep | side K img_f32 kernel n_chains [...]\n", argv[0]);
+    return 2;
+  }
+  for (int i = 1; i + 4 < argc; i += 5) {
+    const int side = std::atoi(argv[i]), K = std::atoi(argv[i + 1]);
+    const bool f32 = std::atoi(argv[i + 2]) != 0;
+    const int kernel = std::atoi(argv[i + 3]);
+    const int64_t n = std::atoll(argv[i + 4]);
+    std::puts(body_key(image(side, f32, kernel), K, n).c_str());
+  }
+  return 0;
+}

@@ -12,6 +12,7 @@
 #pragma once
 #include "rhmc.h"
 #include "rhmc_wave.hpp"
+#include <type_traits>
 
 #ifdef RHMC_MARKS
 #define RHMC_MARK(n) asm volatile("s_setprio " #n ::: "memory")
@@ -51,6 +52,13 @@ struct LeapArgsK1 {
   Consts c;
 };
 
+// FLAT (the one-star step loop): no divergent region.  `low` is applied as a
+// select, so 1/(f + c0) and 1/s are scheduled together in one basic block
+// instead of one block each, and the prior's own 1/f is evaluated only when
+// the prior is on (wave-uniform test, which the compiler places after 1/fl)
+// and only in lanes below f_low.  Same operations on the same operands: the
+// values are those of the branching form bit for bit.
+template <bool FLAT = false>
 __device__ __forceinline__ FluxMetric flux_metric(double f, const Consts& c,
                                                   const LeanConsts& l) {
   FluxMetric m;
@@ -62,10 +70,25 @@ __device__ __forceinline__ FluxMetric flux_metric(double f, const Consts& c,
   const double fl = low ? l.f_low : f;
   const double u = rcp_nr(fl);
   m.s = u * fma(l.Bg2, u, l.inv_g1);
-  const double t2 = low ? 0.0 : (u * u) * fma(l.two_Bg2, u, l.inv_g1) * rcp_nr(m.s);
+  double t2;
+  if constexpr (FLAT) {
+    const double t2f = (u * u) * fma(l.two_Bg2, u, l.inv_g1) * rcp_nr(m.s);
+    t2 = low ? 0.0 : t2f;
+  } else {
+    t2 = low ? 0.0 : (u * u) * fma(l.two_Bg2, u, l.inv_g1) * rcp_nr(m.s);
+  }
   const double t1 = -m.A * (ib * ib);
   m.mterm = (t1 + 2.0 * t2) / 2.0;
-  m.prior = c.use_prior ? c.alpha * (low ? rcp_nr(f) : u) : 0.0;
+  if constexpr (FLAT) {  // last, so that the test does not split the chains above
+    m.prior = 0.0;
+    if (__builtin_expect(c.use_prior != 0, 0)) {
+      double uf = u;
+      if (low) uf = rcp_nr(f);
+      m.prior = c.alpha * uf;
+    }
+  } else {
+    m.prior = c.use_prior ? c.alpha * (low ? rcp_nr(f) : u) : 0.0;
+  }
   return m;
 }
 
@@ -105,7 +128,10 @@ __device__ __forceinline__ void q_loop_lanes16(double& f, double& x, double& y, 
   const double b4 = b2 * b2, c4 = fma(b2, c2, c2);
   int n = 0;
   bool done = false, more = false;
-  do {
+  // One pass.  FIRST: the peeled first pass (n == 0, no chain done), straight-
+  // line without the loop-carried selects.
+  auto pass = [&](auto first) {
+    constexpr bool FIRST = decltype(first)::value;
     double Fj = f;
     if (j & 1) Fj = fma(bf, Fj, cf);
     if (j & 2) Fj = fma(b2, Fj, c2);
@@ -123,7 +149,7 @@ __device__ __forceinline__ void q_loop_lanes16(double& f, double& x, double& y, 
     const double a0 = fabs(Fj - Fj1), a1 = fabs(Xj - Xj1), a2 = fabs(Yj - Yj1);
     const double sum = a0 + a1 + a2;
     const bool go = (fmax(fmax(a0, a1), a2) > c.delta) && (sum == sum);
-    const bool stop = !go || (n + j + 1 >= c.counter_max);
+    const bool stop = !go || ((FIRST ? 0 : n) + j + 1 >= c.counter_max);
     const unsigned long long bal = __builtin_amdgcn_ballot_w64(stop);
     const unsigned bits = (unsigned)(bal >> gsh) & 0xFFu;
     const int k = bits ? (int)__builtin_ctz(bits) : 7;
@@ -131,15 +157,23 @@ __device__ __forceinline__ void q_loop_lanes16(double& f, double& x, double& y, 
     const double nf = __shfl(Fj1, src, kWave), nx = __shfl(Xj1, src, kWave),
                  ny = __shfl(Yj1, src, kWave);
     const int ngo = __shfl((int)go, src, kWave);
-    if (!done) {
+    if (FIRST || !done) {
       f = nf;
       x = nx;
       y = ny;
-      n += k + 1;
+      n = (FIRST ? 0 : n) + k + 1;
       more = ngo != 0;
       done = bits != 0u;
     }
-  } while (__builtin_amdgcn_ballot_w64(!done) != 0);
+  };
+  // Nearly every step needs one pass (3.7 iterations on average at C2): the
+  // loop is the rare continuation, behind one wave-uniform test.
+  pass(std::true_type{});
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!done) != 0, 0)) {
+    do {
+      pass(std::false_type{});
+    } while (__builtin_amdgcn_ballot_w64(!done) != 0);
+  }
   it_q += n;
   if (more) st |= RHMC_STATUS_QLOOP_CAP;
 }
@@ -156,7 +190,7 @@ __device__ __forceinline__ void k1_steps(double& f, double& x, double& y, double
                                          int& it_p, int& it_q, unsigned& st,
                                          long long* prof = nullptr) {
   const double hdt = c.hdt;
-  FluxMetric fm = flux_metric(f, c, lc);
+  FluxMetric fm = flux_metric<true>(f, c, lc);
   long long t0 = 0;
   // phase boundary: fenced clock read; the cycles since the last boundary go
   // to bucket `close` (a constant at every call site)
@@ -211,7 +245,7 @@ __device__ __forceinline__ void k1_steps(double& f, double& x, double& y, double
       const double rho = pf, hc = hdt * (fm.coef * 0.5);
       int n = 0;
       bool more;
-      do {
+      auto pass = [&]() {
         double P[kSpecP + 1];
         bool go[kSpecP];
         P[0] = pf;
@@ -233,7 +267,14 @@ __device__ __forceinline__ void k1_steps(double& f, double& x, double& y, double
         }
         pf = sel;
         n += take;
-      } while (more && n < c.counter_max);
+      };
+      // the first pass straight-line (1.85 iterations per step on average at
+      // C2); later passes are the rare continuation
+      pass();
+      if (__builtin_expect(more && n < c.counter_max, 0)) {
+        do pass();
+        while (more && n < c.counter_max);
+      }
       it_p += n;
       if (more) st |= RHMC_STATUS_PLOOP_CAP;
       RHMC_MARK(3);
@@ -298,7 +339,7 @@ __device__ __forceinline__ void k1_steps(double& f, double& x, double& y, double
       RHMC_MARK(4);
     }
     mark(2);
-    fm = flux_metric(f, c, lc);
+    fm = flux_metric<true>(f, c, lc);
     pf = pf - hdt * ((pf * pf) * fm.coef / 2.0);   // :548
     RHMC_MARK(5);
   }

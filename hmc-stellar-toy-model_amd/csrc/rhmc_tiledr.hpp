@@ -123,7 +123,8 @@ struct TiledR {
 
   // Make the cached window pixels those of the window at (x, y): re-read them
   // from the LDS image when round(x) or round(y) moved (wave-uniform branch).
-  static __device__ __forceinline__ void ensure(const DT* __restrict__ sD, Cache& k, double x,
+  // Returns whether the wave reloaded (wave-uniform; the PROF build counts it).
+  static __device__ __forceinline__ bool ensure(const DT* __restrict__ sD, Cache& k, double x,
                                                 double y) {
     const int m = lane_id() % LPC;
     const int a = m / 4, b = m % 4;
@@ -139,7 +140,9 @@ struct TiledR {
       k.c0 = (double)c0;
       bounds(x, k.xlo, k.xhi);
       bounds(y, k.ylo, k.yhi);
+      return true;
     }
+    return false;
   }
 
   // The PSF factors of this lane's window rows (ex) and columns (ey, with the
@@ -281,7 +284,8 @@ struct TiledR {
   // factors carry f (fey = f ey serves Lambda and both sums), so no separate
   // f ex row factors are held: 14 VGPRs and 7 products fewer.
   // PROFG (tools only): fenced clock reads split the gradient into gp[3] window
-  // check, gp[0] PSF factors, gp[1] pixel loop, gp[2] moments + reductions.
+  // check, gp[0] PSF factors, gp[1] pixel loop, gp[2] moments + reductions;
+  // gp[4] is the window check's share on the steps that reload, gp[5] their number.
   template <bool PROFG = false>
   static __device__ __forceinline__ void partial(const double* __restrict__ etab,
                                                  const DT* __restrict__ sD, Cache& k, double f,
@@ -302,8 +306,15 @@ struct TiledR {
     const int m = lane_id() % LPC;
     const int a = m / 4, b = m % 4;
     double ex[TR], ey[TC];
-    ensure(sD, k, x, y);
-    gmark(3);
+    const bool reloaded = ensure(sD, k, x, y);
+    if constexpr (PROFG) {
+      const long long before = gp[3];
+      gmark(3);
+      if (reloaded) {
+        gp[4] += gp[3] - before;
+        gp[5] += 1;
+      }
+    }
     fs = flux_fold(f);
     factors_rec(etab, k, x, y, lc, fs, ex, ey);  // ey carries fs (= f but at |f| < 2^-547)
     const double r0 = k.r0, c0 = k.c0;
@@ -472,7 +483,7 @@ leapfrog_k1_tiledr(LeapArgsK1 a) {
   TL::init(cache);
   int it_p = 0, it_q = 0;
   unsigned st = 0u;
-  long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long long prof[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   k1_steps<PROF, TL::LPC>(f, x, y, pf, px, py, a.n_steps, (double)(IMG - 1), c, lc,
                  [&](double f_, double x_, double y_, double& gf, double& gx, double& gy) {
                    TL::template gradient<PROF>(lds, simg, cache, f_, x_, y_, c, lc, gf, gx, gy,
@@ -489,6 +500,9 @@ leapfrog_k1_tiledr(LeapArgsK1 a) {
     py = prof[5] / ns;  // pixel loop (prof[6], moments + reductions: it_p)
     it_p = (int)(prof[6] / ns);
     it_q = (int)(prof[7] / ns);  // window check
+    // ... split: status = steps that reloaded | their mean window-check cycles << 16
+    const long long rc = prof[9] > 0 ? prof[8] / prof[9] : 0;
+    st = (unsigned)(prof[9] & 0xFFFF) | ((unsigned)(rc > 0xFFFF ? 0xFFFF : rc) << 16);
   }
 
   if ((lane % TL::LPC) == 0 && real) {

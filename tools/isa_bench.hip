@@ -86,6 +86,53 @@ __global__ void thr(double* out, double seed, int iters) {
   out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;
 }
 
+// Branch costs with nothing to hide them (run at one wave per SIMD): 8 per
+// iteration.  A taken branch jumps over PAD never-executed bytes of s_nop, as
+// a step's common path jumps over an out-of-line block; the not-taken forms
+// branch backwards to their own compare and never go.
+//  0 s_cmp + s_nop (floor)      1 s_cmp + s_cbranch_scc1 not taken
+//  2 s_cmp + s_cbranch_scc1 taken, 1.5 KB ahead   3 s_branch, 1.5 KB ahead
+//  4 v_cmp_lt_f64 -> s_cbranch_vccz not taken     5 v_cmp_lt_f64 -> s_cbranch_vccnz taken, 1.5 KB
+#define ISA_PAD ".rept 384\n s_nop 0\n .endr\n"
+template <int MODE>
+__global__ void brk(double* out, double seed, int iters, int one) {
+  const double a = seed + threadIdx.x * 1e-3, b = a + 1.0;  // a < b in every lane
+  for (int i = 0; i < iters; ++i) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (MODE == 0) asm volatile("s_cmp_eq_u32 %0, 0\n s_nop 0" ::"s"(one) : "scc");
+      if (MODE == 1) asm volatile("1:\n s_cmp_eq_u32 %0, 0\n s_cbranch_scc1 1b" ::"s"(one) : "scc");
+      if (MODE == 2)
+        asm volatile("s_cmp_lg_u32 %0, 0\n s_cbranch_scc1 1f\n" ISA_PAD "1:" ::"s"(one) : "scc");
+      if (MODE == 3) asm volatile("s_branch 1f\n" ISA_PAD "1:" ::"s"(one));
+      if (MODE == 4)
+        asm volatile("1:\n v_cmp_lt_f64 vcc, %0, %1\n s_cbranch_vccz 1b" ::"v"(a), "v"(b) : "vcc");
+      if (MODE == 5)
+        asm volatile("v_cmp_lt_f64 vcc, %0, %1\n s_cbranch_vccnz 1f\n" ISA_PAD "1:" ::"v"(a), "v"(b)
+                     : "vcc");
+    }
+  }
+  out[blockIdx.x * blockDim.x + threadIdx.x] = a + b;
+}
+
+template <int MODE>
+float run_br(int blocks, int iters) {
+  double* out;
+  hipMalloc(&out, (size_t)blocks * 64 * 8);
+  hipEvent_t a, b;
+  hipEventCreate(&a);
+  hipEventCreate(&b);
+  brk<MODE><<<blocks, 64>>>(out, 1.5, 10, 1);
+  hipEventRecord(a);
+  brk<MODE><<<blocks, 64>>>(out, 1.5, iters, 1);
+  hipEventRecord(b);
+  hipEventSynchronize(b);
+  float ms;
+  hipEventElapsedTime(&ms, a, b);
+  hipFree(out);
+  return ms;
+}
+
 __global__ void rcp_acc(const double* x, unsigned long long* stat, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -178,6 +225,15 @@ int main() {
       printf("waves/SIMD %d  %-14s %8.3f ms  %6.2f cycles/wave-op @%.1fGHz\n", wps, names[m],
              t[m], t[m] * 1e-3 * ghz * 1e9 / ops, ghz);
     }
+  }
+  {
+    const char* bn[] = {"s_cmp + s_nop", "scc br not taken", "scc br taken 1.5K", "s_branch 1.5K",
+                        "v_cmp->vccz not tk", "v_cmp->vccnz tk 1.5K"};
+    const float bt[] = {run_br<0>(simds, iters), run_br<1>(simds, iters), run_br<2>(simds, iters),
+                        run_br<3>(simds, iters), run_br<4>(simds, iters), run_br<5>(simds, iters)};
+    for (int m = 0; m < 6; ++m)
+      printf("waves/SIMD 1  %-20s %8.3f ms  %6.2f cycles/branch @%.1fGHz\n", bn[m], bt[m],
+             bt[m] * 1e-3 * ghz * 1e9 / (8.0 * iters), ghz);
   }
   const int n = 1 << 24;
   std::vector<double> hx(n);

@@ -1,15 +1,20 @@
 // traj_bodies.cpp — which kernel body serves a random-length trajectory
-// (rhmc_hmc_random, rhmc_diag_random).  Host-only, csrc/rhmc_select.hpp alone:
-// select(..., Op::HmcRandom, ...) gives the plan, and body_key() names the
-// instantiation that csrc/rhmc_launch.hpp's switches (launch_hmc_random_t,
-// launch_k1_w28, launch_multi, launch_kr, with_path) launch for it:
+// (rhmc_hmc_random, rhmc_diag_random) or, with the leading word `integrate`,
+// an explicit integrator (rhmc_integrate with RHMC_SOLVER_HMC, _RHMC_NAIVE or
+// _RHMC_LEAPFROG).  Host-only, csrc/rhmc_select.hpp alone: select(...,
+// Op::HmcRandom or Op::Integrate, ...) gives the plan, and body_key() names the
+// instantiation that csrc/rhmc_launch.hpp's switches (launch_hmc_random_t or
+// launch_integrate, then launch_k1_w28, launch_multi, launch_kr, with_path)
+// launch for it; the integrators build each body once per solver:
 //   regwin1/IMG/DT          (diag_)hmc_random_k1_tiledr<IMG, DT>
+//                           integrate_k1_tiledr<IMG, 28, DT, SOLVER>
 //   pixmajor/IMG            leapfrog_pk<IMG, 10, SOLVER>
 //   multiwin/DT/SLOTS/TAB   leapfrog_kr<DT, SLOTS, TAB, SOLVER, 1>
 //   slotted/POLICY/SLOTS    (diag_)hmc_random_win_kernel<G, SLOTS>
-// Built and run by tests/test_traj_bodies.py.
-//   traj_bodies sweep                                  the distinct keys
-//   traj_bodies side K img_f32 kernel n_chains [...]   one key per group of five
+//                           integrate_win_kernel<G, SOLVER, SLOTS>
+// Built and run by tests/test_traj_bodies.py and tests/test_integrate_bodies.py.
+//   traj_bodies [integrate] sweep                                  the distinct keys
+//   traj_bodies [integrate] side K img_f32 kernel n_chains [...]   one key per group of five
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,9 +36,9 @@ static SelectIn image(int side, bool f32, int kernel) {
   return s;
 }
 
-static std::string body_key(const SelectIn& s, int K, int64_t n) {
+static std::string body_key(Op op, const SelectIn& s, int K, int64_t n) {
   const double sigma = 3.5 / 2.354;  // the reference PSF, FWHM 3.5 px
-  const Plan pl = select(s, /*use_Vc*/ false, 1.0 / (2.0 * sigma * sigma), Op::HmcRandom, K, n);
+  const Plan pl = select(s, /*use_Vc*/ false, 1.0 / (2.0 * sigma * sigma), op, K, n);
   const std::string side = std::to_string(s.rows);
   switch (pl.family) {
     case Family::Unsupported: return "Unsupported";
@@ -49,7 +54,7 @@ static std::string body_key(const SelectIn& s, int K, int64_t n) {
       if (pl.tables) return std::string("multiwin/") + dt + "/1/tab";
       return std::string("multiwin/") + dt + (pl.slots == 1 ? "/1/notab" : "/2/notab");
     }
-    default: break;  // launch_hmc_random_t: everything else goes with_path
+    default: break;  // launch_hmc_random_t, launch_integrate: everything else goes with_path
   }
   if (pl.path == 32 || pl.path == 48) {  // with_slots: 1, 2, else 4
     const int sl = win_slots(K);
@@ -63,6 +68,13 @@ static std::string body_key(const SelectIn& s, int K, int64_t n) {
 }
 
 int main(int argc, char** argv) {
+  const char* prog = argv[0];
+  Op op = Op::HmcRandom;
+  if (argc > 1 && !std::strcmp(argv[1], "integrate")) {
+    op = Op::Integrate;
+    --argc;
+    ++argv;
+  }
   if (argc == 2 && !std::strcmp(argv[1], "sweep")) {
     std::set<std::string> keys;
     for (int side : {32, 48, 64, 96})
@@ -70,12 +82,13 @@ int main(int argc, char** argv) {
         for (int f32 = 0; f32 < 2; ++f32)
           for (int kernel = RHMC_KERNEL_AUTO; kernel <= RHMC_KERNEL_DENSE; ++kernel)
             for (int64_t n : {(int64_t)4, (int64_t)65536})
-              keys.insert(body_key(image(side, f32 != 0, kernel), K, n));
+              keys.insert(body_key(op, image(side, f32 != 0, kernel), K, n));
     for (const std::string& k : keys) std::puts(k.c_str());
     return 0;
   }
   if (argc < 6 || (argc - 1) % 5 != 0) {
-    std::fprintf(stderr, "usage: %s sweep | side K img_f32 kernel n_chains [...]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s [integrate] sweep | side K img_f32 kernel n_chains [...]\n",
+                 prog);
     return 2;
   }
   for (int i = 1; i + 4 < argc; i += 5) {
@@ -83,7 +96,7 @@ int main(int argc, char** argv) {
     const bool f32 = std::atoi(argv[i + 2]) != 0;
     const int kernel = std::atoi(argv[i + 3]);
     const int64_t n = std::atoll(argv[i + 4]);
-    std::puts(body_key(image(side, f32, kernel), K, n).c_str());
+    std::puts(body_key(op, image(side, f32, kernel), K, n).c_str());
   }
   return 0;
 }

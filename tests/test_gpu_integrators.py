@@ -140,7 +140,8 @@ def test_explicit_other_image_sides(gpu_lib, side, name):
         assert err_q.max() <= 1e-9 and err_p.max() <= 1e-8, (side, name, k, err_q, err_p)
 
 
-# ---- many stars: the multi-star register-window kernel (leapfrog_kr<..., SOLVER>)
+# ---- many stars: the pixel-major, multi-star register-window and dense kernels
+# (leapfrog_pk / leapfrog_kr<..., SOLVER>, integrate_win_kernel)
 def _star_field(side, K, n_chains, seed):
     """A C3-style workload (big-sim4 parameters, power-law fluxes) on a
     side x side image with K stars."""
@@ -160,10 +161,13 @@ def _star_field(side, K, n_chains, seed):
 
 
 @pytest.mark.parametrize("name", SOLVERS)
-@pytest.mark.parametrize("side,K,n_chains", [(48, 10, 16384),   # C3: LDS factor tables
-                                             (32, 4, 301),      # pixel-major, 32-px image
-                                             (48, 20, 37),      # exp path, one star slot
-                                             (64, 40, 5)])      # two star slots per lane
+# The bodies are those that tests/native/traj_bodies.cpp's `integrate` mode names
+# for these shapes (Poisson images: exact in fp32); every body has its own case
+# in test_gpu_integrate_bodies.py.
+@pytest.mark.parametrize("side,K,n_chains", [(48, 10, 16384),   # C3: pixmajor/48
+                                             (32, 4, 301),      # pixmajor/32
+                                             (48, 20, 37),      # slotted/Dense48/1
+                                             (64, 40, 5)])      # multiwin/float/2/notab
 def test_many_star_explicit_vs_oracle(gpu_lib, name, side, K, n_chains, monkeypatch):
     capi = gpu_lib
     wl = workloads.make("C3") if K == 10 else _star_field(side, K, n_chains, 11 + K)

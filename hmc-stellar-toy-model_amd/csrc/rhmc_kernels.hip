@@ -34,6 +34,7 @@
 #include "rhmc_dense.hpp"
 #include "rhmc_rows.hpp"
 #include "rhmc_perwave.hpp"
+#include "rhmc_hess.hpp"
 
 namespace rhmc {
 // The dense kernel's one-slot leapfrog (K <= 64 on 32/48-px images: B4, the
@@ -168,6 +169,38 @@ int check_diag(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* o, con
       return fail(RHMC_ERR_ARG, "opts.trace_rows = " + std::to_string(o->trace_rows) +
                                     " must exceed the longest trajectory (" +
                                     std::to_string(longest) + " steps)");
+  }
+  if (!ctx) return fail(RHMC_ERR_ARG, "ctx is NULL");
+  if (n > 0 && !ctx->d_D) return fail(RHMC_ERR_ARG, "no image uploaded");
+  return RHMC_OK;
+}
+
+// The checks the hess_derivs / hess_random entry points share (n == 0 after
+// them: a no-op), arguments before the context like check_peaks.  traj: the
+// trajectory's arguments (opts, p, steps; f_lim >= 0, which the break test of
+// hess_trajectory relies on); host_call: steps is readable.
+int check_hess(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_hess_opts* o, const double* q,
+               const double* p, const int32_t* steps, int64_t n, int32_t K, bool traj,
+               bool host_call) {
+  if (!P) return fail(RHMC_ERR_ARG, "params is NULL");
+  if (traj && !o) return fail(RHMC_ERR_ARG, "opts is NULL");
+  if (n < 0) return fail(RHMC_ERR_ARG, "n_chains < 0");
+  if (n > ((int64_t)1 << 40)) return fail(RHMC_ERR_ARG, "n_chains too large");
+  if (K < 1 || K > kMaxK) return fail(RHMC_ERR_ARG, "K must be in [1, 1024]");
+  if (traj) {
+    if (o->reserved[0] != 0 || o->reserved[1] != 0)
+      return fail(RHMC_ERR_ARG, "opts.reserved must be 0");
+    if (!(std::isfinite(o->dt_f) && std::isfinite(o->dt_xy)))
+      return fail(RHMC_ERR_ARG, "opts.dt_f / opts.dt_xy is not finite");
+    if (!(P->f_lim >= 0.0))
+      return fail(RHMC_ERR_ARG, "params.f_lim must be >= 0 for the Hessian-metric trajectory");
+    if (!steps) return fail(RHMC_ERR_ARG, "steps is NULL");
+    if (n > 0 && (!q || !p)) return fail(RHMC_ERR_ARG, "q/p is NULL");
+    if (host_call)
+      for (int64_t i = 0; i < n; ++i)
+        if (steps[i] < 1) return fail(RHMC_ERR_ARG, "steps[i] must be >= 1");
+  } else if (n > 0 && !q) {
+    return fail(RHMC_ERR_ARG, "q is NULL");
   }
   if (!ctx) return fail(RHMC_ERR_ARG, "ctx is NULL");
   if (n > 0 && !ctx->d_D) return fail(RHMC_ERR_ARG, "no image uploaded");
@@ -768,6 +801,72 @@ int rhmc_diag_random(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* 
     return launch_diag_random(ctx, P, opts, st.dev<double>(iq), st.dev<double>(ip),
                               st.dev<int32_t>(in), n_chains, K, st.dev<int32_t>(is),
                               st.dev<double>(it), ctx->stream);
+  });
+}
+
+int rhmc_hess_derivs_device(rhmc_ctx* ctx, const rhmc_params* P, const double* d_q,
+                            double* d_dVdq, double* d_dVdqq, double* d_dVdqqq, double* d_V,
+                            int64_t n_chains, int32_t K, void* stream) {
+  if (int rc = check_hess(ctx, P, nullptr, d_q, nullptr, nullptr, n_chains, K, false, false))
+    return rc;
+  if (n_chains == 0) return RHMC_OK;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  return launch_hess(ctx, P, nullptr, const_cast<double*>(d_q), nullptr, nullptr, n_chains, K,
+                     nullptr, nullptr, d_dVdq, d_dVdqq, d_dVdqqq, d_V, s);
+}
+
+int rhmc_hess_derivs(rhmc_ctx* ctx, const rhmc_params* P, const double* q, double* dVdq,
+                     double* dVdqq, double* dVdqqq, double* V, int64_t n_chains, int32_t K) {
+  if (int rc = check_hess(ctx, P, nullptr, q, nullptr, nullptr, n_chains, K, false, true))
+    return rc;
+  if (n_chains == 0) return RHMC_OK;
+  const size_t sb = (size_t)n_chains * 3 * K * sizeof(double);
+  HIP_TRY(hipSetDevice(ctx->device));
+  Staging st(ctx);  // an output not asked for has no part (NULL to the kernel)
+  const int iq = st.add(q, sb, Staging::kIn);
+  const int i1 = st.add(dVdq, dVdq ? sb : 0, Staging::kOut);
+  const int i2 = st.add(dVdqq, dVdqq ? sb : 0, Staging::kOut);
+  const int i3 = st.add(dVdqqq, dVdqqq ? sb : 0, Staging::kOut);
+  const int iV = st.add(V, V ? (size_t)n_chains * sizeof(double) : 0, Staging::kOut);
+  return st.run([&] {
+    return launch_hess(ctx, P, nullptr, st.dev<double>(iq), nullptr, nullptr, n_chains, K,
+                       nullptr, nullptr, st.dev<double>(i1), st.dev<double>(i2),
+                       st.dev<double>(i3), st.dev<double>(iV), ctx->stream);
+  });
+}
+
+int rhmc_hess_random_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_hess_opts* opts,
+                            double* d_q, double* d_p, const int32_t* d_steps, int64_t n_chains,
+                            int32_t K, int32_t* d_status, int32_t* d_steps_done, double* d_dVdq,
+                            double* d_dVdqq, double* d_dVdqqq, void* stream) {
+  if (int rc = check_hess(ctx, P, opts, d_q, d_p, d_steps, n_chains, K, true, false)) return rc;
+  if (n_chains == 0) return RHMC_OK;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  return launch_hess(ctx, P, opts, d_q, d_p, d_steps, n_chains, K, d_status, d_steps_done,
+                     d_dVdq, d_dVdqq, d_dVdqqq, nullptr, s);
+}
+
+int rhmc_hess_random(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_hess_opts* opts, double* q,
+                     double* p, const int32_t* steps, int64_t n_chains, int32_t K,
+                     int32_t* status, int32_t* steps_done, double* dVdq, double* dVdqq,
+                     double* dVdqqq) {
+  if (int rc = check_hess(ctx, P, opts, q, p, steps, n_chains, K, true, true)) return rc;
+  if (n_chains == 0) return RHMC_OK;
+  const size_t sb = (size_t)n_chains * 3 * K * sizeof(double);
+  const size_t tb = (size_t)n_chains * sizeof(int32_t);
+  HIP_TRY(hipSetDevice(ctx->device));
+  Staging st(ctx);  // an output not asked for has no part (NULL to the kernel)
+  const int iq = st.add(q, sb, Staging::kInOut), ip = st.add(p, sb, Staging::kInOut);
+  const int in = st.add(steps, tb, Staging::kIn);
+  const int is = st.add(status, status ? tb : 0, Staging::kOut);
+  const int id = st.add(steps_done, steps_done ? tb : 0, Staging::kOut);
+  const int i1 = st.add(dVdq, dVdq ? sb : 0, Staging::kOut);
+  const int i2 = st.add(dVdqq, dVdqq ? sb : 0, Staging::kOut);
+  const int i3 = st.add(dVdqqq, dVdqqq ? sb : 0, Staging::kOut);
+  return st.run([&] {
+    return launch_hess(ctx, P, opts, st.dev<double>(iq), st.dev<double>(ip), st.dev<int32_t>(in),
+                       n_chains, K, st.dev<int32_t>(is), st.dev<int32_t>(id), st.dev<double>(i1),
+                       st.dev<double>(i2), st.dev<double>(i3), nullptr, ctx->stream);
   });
 }
 

@@ -1039,6 +1039,42 @@ int launch_diag_random(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts
   return launch_hmc_random_t<true>(ctx, c, nullptr, d_q, d_p, d_steps, n, K, d_st, s, dg);
 }
 
+// RHMC_random's kernels (rhmc_hess.hpp; the entry points' checks have passed):
+// the trajectory with `o`, else the derivative sets at d_q.  One wave per
+// chain, select_hess()'s waves per workgroup and LDS bytes.
+int launch_hess(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_hess_opts* o, double* d_q,
+                double* d_p, const int32_t* d_steps, int64_t n, int32_t K, int32_t* d_st,
+                int32_t* d_done, double* d_dVdq, double* d_dVdqq, double* d_dVdqqq, double* d_V,
+                hipStream_t s) {
+  HessArgs a;
+  int rc = make_consts(P, &a.c);
+  if (rc) return rc;
+  const HessPlan pl = select_hess(select_in(ctx), K);
+  if (pl.message) return fail(RHMC_ERR_UNSUPPORTED, pl.message);
+  const int64_t blocks = (n + pl.waves - 1) / pl.waves;
+  if (blocks > 0x7fffffff) return fail(RHMC_ERR_UNSUPPORTED, "n_chains exceeds one launch's grid");
+  a.q = d_q;
+  a.p = d_p;
+  a.steps = d_steps;
+  a.status = d_st;
+  a.steps_done = d_done;
+  a.dVdq = d_dVdq;
+  a.dVdqq = d_dVdqq;
+  a.dVdqqq = d_dVdqqq;
+  a.V = d_V;
+  a.D = ctx->d_D;
+  a.n_chains = n;
+  a.K = K;
+  a.dt_f = o ? o->dt_f : 0.0;
+  a.dt_xy = o ? o->dt_xy : 0.0;
+  a.g = make_geometry(ctx->rows, ctx->cols);
+  HIP_TRY(hipSetDevice(ctx->device));
+  const dim3 grid((unsigned)blocks), block(pl.waves * kWave);
+  if (o) hipLaunchKernelGGL(hess_random_kernel, grid, block, pl.lds_bytes, s, a);
+  else hipLaunchKernelGGL(hess_derivs_kernel, grid, block, pl.lds_bytes, s, a);
+  return launch_status();
+}
+
 // ---------------------------------------------------------------------------
 // find_peaks' seed descent (rhmc_peaks.hpp)
 // ---------------------------------------------------------------------------

@@ -319,6 +319,50 @@ inline DtPlan select_dt(const SelectIn& s) {
   return pl;
 }
 
+// The Hessian-metric kernels (rhmc_hess.hpp: hess_derivs_kernel,
+// hess_random_kernel): one wave per chain, pixel-major over the full image.
+// LDS: the fp64 image once per workgroup, and per wave the four factor tables
+// of rhmc_perwave.hpp (2 K (rows + cols) doubles), the 1 / Lambda image
+// (side^2 doubles) and the stars' fluxes (kMaxKGeneric doubles).  Served:
+// 1 <= K <= 16 on square images of side 16..48; `waves` is the largest of 4, 2,
+// 1 waves per workgroup that fits the device's LDS (48 px: four waves up to 11
+// stars, 160,256 B there; two from 12 stars, 104,704 B at 16).  RHMC_OPT_KERNEL
+// does not enter.
+constexpr int kHessMinSide = 16, kHessMaxSide = 48;
+
+constexpr size_t hess_wave_doubles(int K, int side) {
+  return table_doubles(K, side, side) + (size_t)side * side + kMaxKGeneric;
+}
+
+struct HessPlan {
+  int waves = 0;                   // waves (chains) per workgroup
+  size_t lds_bytes = 0;
+  const char* message = nullptr;   // set: RHMC_ERR_UNSUPPORTED
+};
+
+inline HessPlan select_hess(const SelectIn& s, int K) {
+  HessPlan pl;
+  if (s.rows != s.cols || s.rows < kHessMinSide || s.rows > kHessMaxSide) {
+    pl.message = "the Hessian-metric kernels serve square images of side 16..48";
+    return pl;
+  }
+  if (K < 1 || K > kMaxKGeneric) {
+    pl.message = "the Hessian-metric kernels serve 1 <= K <= 16";
+    return pl;
+  }
+  const size_t img = (size_t)s.rows * s.cols;
+  for (int W = 4; W >= 1; W >>= 1) {
+    const size_t need = (img + W * hess_wave_doubles(K, s.rows)) * sizeof(double);
+    if (need <= (size_t)s.max_lds) {
+      pl.waves = W;
+      pl.lds_bytes = need;
+      return pl;
+    }
+  }
+  pl.message = "the Hessian-metric kernels' image and tables exceed the device's LDS";
+  return pl;
+}
+
 // The kernel family and its compile-time choices for one call.
 inline Plan select(const SelectIn& s, bool use_Vc, double inv_two_sig2, Op op, int K,
                    int64_t n_chains) {

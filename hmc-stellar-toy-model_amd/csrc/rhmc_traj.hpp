@@ -1,6 +1,7 @@
 // rhmc_traj.hpp — the random-length trajectory of samplers.lightsource_gym's
 // HMC_random (samplers.py:519-552) and RHMC_random_diag (:766-800), once for
-// every kernel family.  Included from rhmc_wave.hpp (DiagArgs, diag_force_f,
+// every kernel family (random_trajectory), and RHMC_random's (:1016-1067,
+// hess_trajectory).  Included from rhmc_wave.hpp (DiagArgs, diag_force_f,
 // diag_drift).
 #pragma once
 
@@ -107,6 +108,102 @@ __device__ __forceinline__ bool random_trajectory(double (&f)[SLOTS], double (&x
     }
   }
   return flip;
+}
+
+// One star's derivative sets of RHMC_efficient_computation (samplers.py:881-903):
+// dVdq, dVdqq and dVdqqq for (f, x, y).
+struct HessD {
+  double d1f, d1x, d1y, d2f, d2x, d2y, d3f, d3x, d3y;
+};
+
+// RHMC_random's trajectory (samplers.py:1016-1067) for one star per lane:
+// leapfrog under the metric diag(dVdqq), the force with dVdqqq, steps dt_f for
+// f and dt_xy for x and y.  On entry (f, x, y) and (pf, px, py) are the start;
+// on return q is the end state, p the reference's p_half, D the derivative
+// sets at the end q; the return value is the number of completed steps.
+// The reference's quirks, all kept:
+//   * dVdqq is used as it comes, negative or zero included: nothing guards the
+//     divisions, NaN and inf propagate (:909-911);
+//   * below the wall RHMC_efficient_computation returns three scalar infs
+//     (:836-837), so every coordinate's dpdt is +inf there: a chain that starts
+//     below it gets p + dt inf / 2 (:1016) and does no step, and after a
+//     crossing in mid-trajectory p_half += dt' inf (:1058) leaves +-inf, or NaN
+//     where dt' is 0, in every entry that is not flagged;
+//   * a step begins with the test E(q, p_half) == +inf (:1024-1027) and breaks
+//     on it.  V is finite or NaN while f_lim >= 0, so the test holds iff some
+//     f < f_lim, or K (:911) is +inf and every coordinate of q is finite: no
+//     logarithm per pixel, one per chain and step (the callers refuse
+//     f_lim < 0);
+//   * the two calls of a step (:1024, :1054) and the first call of the next
+//     step differ only in p: derivs() runs once per step;
+//   * the flux flag is sticky per star and applied on every step in which ANY
+//     star of the chain is below the wall (:1035-1037, :1060-1061);
+//   * the position flags test (x < 0) or (x < num_rows), y against num_rows
+//     too (:1038-1043): true for every coordinate below the side, so px and py
+//     of a star inside the image are replaced by their negatives on every step
+//     and never receive the force; a star at x >= num_rows or NaN does not set
+//     the switch but, once flagged, is still flipped when another star sets it
+//     (:1063-1067);
+//   * the last step adds dt / 2 (:1046-1047) and there is no closing un-kick;
+//     the flagged entries take -p_half from before the update (:1057).
+// What the kernel does its own way comes in as callables:
+//   own()       the lane has a star
+//   any(b)      b of any lane of the chain
+//   sum(v)      v summed over the chain's lanes
+//   prod()      dVdqq's running product over the chain in index order (:911)
+//   derivs(D)   D at the current (f, x, y)
+template <class OWN, class ANY, class SUM, class PROD, class DERIVS>
+__device__ __forceinline__ int hess_trajectory(double& f, double& x, double& y, double& pf,
+                                               double& px, double& py, int n, double f_lim,
+                                               double side, double dt_f, double dt_xy, HessD& D,
+                                               bool& flag_f, bool& flag_xy, OWN own, ANY any,
+                                               SUM sum, PROD prod, DERIVS derivs) {
+  const double inf = __builtin_inf();
+  const bool me = own();
+  auto dpdt = [&](bool wall, double p, double d1, double d2, double d3) RHMC_INLINE_LAMBDA {
+    const double dqdt = p / d2;                                      // :909
+    const double v = -d3 * ((1. / d2) - dqdt * dqdt) / 2. - d1;      // :910
+    return wall ? inf : v;
+  };
+  derivs(D);
+  bool wall = any(me && f < f_lim);                // :832-837
+  pf = pf + dt_f * dpdt(wall, pf, D.d1f, D.d2f, D.d3f) / 2.;   // :1016
+  px = px + dt_xy * dpdt(wall, px, D.d1x, D.d2x, D.d3x) / 2.;
+  py = py + dt_xy * dpdt(wall, py, D.d1y, D.d2y, D.d3y) / 2.;
+  bool iflip = false, iflip_x = false, iflip_y = false;
+  int done = 0;
+  for (int z = 0; z < n; ++z) {
+    const double kin =
+        sum(me ? (pf * pf) / D.d2f + (px * px) / D.d2x + (py * py) / D.d2y : 0.0);
+    const double K = kin / 2. + log(prod()) / 2.;                    // :911
+    const bool q_finite = !any(me && !(isfinite(f) && isfinite(x) && isfinite(y)));
+    if (wall || (K == inf && q_finite)) break;                       // :1025-1027
+    f = f + dt_f * (pf / D.d2f);                                     // :1031
+    x = x + dt_xy * (px / D.d2x);
+    y = y + dt_xy * (py / D.d2y);
+    const bool below = me && f < f_lim;                              // :1035
+    const bool in_x = me && (x < 0.0 || x < side);                   // :1038
+    const bool in_y = me && (y < 0.0 || y < side);                   // :1041
+    iflip = iflip || below;
+    iflip_x = iflip_x || in_x;
+    iflip_y = iflip_y || in_y;
+    const bool flip = any(below), flip_x = any(in_x), flip_y = any(in_y);
+    wall = flip;
+    derivs(D);                                                       // :1054
+    const bool last = z == n - 1;                                    // :1046-1049
+    const double tf = last ? dt_f / 2. : dt_f, txy = last ? dt_xy / 2. : dt_xy;
+    const double kf = -pf, kx = -px, ky = -py;                       // :1057
+    pf = pf + tf * dpdt(wall, pf, D.d1f, D.d2f, D.d3f);              // :1058
+    px = px + txy * dpdt(wall, px, D.d1x, D.d2x, D.d3x);
+    py = py + txy * dpdt(wall, py, D.d1y, D.d2y, D.d3y);
+    if (flip && iflip) pf = kf;                                      // :1060-1067
+    if (flip_x && iflip_x) px = kx;
+    if (flip_y && iflip_y) py = ky;
+    ++done;
+  }
+  flag_f = iflip;
+  flag_xy = iflip_x || iflip_y;
+  return done;
 }
 
 }  // namespace rhmc

@@ -63,7 +63,9 @@ EXPORTS = ("rhmc_abi_version", "rhmc_device_count", "rhmc_last_error",
            "rhmc_rows_copy_device", "rhmc_kinetic_rows_device",
            "rhmc_find_peaks", "rhmc_find_peaks_device",
            "rhmc_dt_trials", "rhmc_dt_trials_device",
-           "rhmc_diag_random", "rhmc_diag_random_device")
+           "rhmc_diag_random", "rhmc_diag_random_device",
+           "rhmc_hess_derivs", "rhmc_hess_derivs_device",
+           "rhmc_hess_random", "rhmc_hess_random_device")
 ABI_VERSION = 4
 
 V_FLUX_WALL = 1       # rhmc_energy f_pos bits (include/rhmc.h)
@@ -142,6 +144,12 @@ class DiagOpts(ctypes.Structure):
     """Mirror of `rhmc_diag_opts` (include/rhmc.h)."""
     _fields_ = [("dt", ctypes.c_double), ("factor1", ctypes.c_double),
                 ("trace_rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class HessOpts(ctypes.Structure):
+    """Mirror of `rhmc_hess_opts` (include/rhmc.h)."""
+    _fields_ = [("dt_f", ctypes.c_double), ("dt_xy", ctypes.c_double),
+                ("reserved", ctypes.c_int32 * 2)]
 
 
 def make_schedule(schedule_g_ff2=None, schedule_beta=None):
@@ -252,6 +260,15 @@ def _load():
                                             ctypes.c_int64, ctypes.c_int32, vp, vp]),
         "rhmc_diag_random_device": (ctypes.c_int, [vp, P(RhmcParams), P(DiagOpts), vp, vp, vp,
                                                    ctypes.c_int64, ctypes.c_int32, vp, vp, vp]),
+        "rhmc_hess_derivs": (ctypes.c_int, [vp, P(RhmcParams), vp, vp, vp, vp, vp,
+                                            ctypes.c_int64, ctypes.c_int32]),
+        "rhmc_hess_derivs_device": (ctypes.c_int, [vp, P(RhmcParams), vp, vp, vp, vp, vp,
+                                                   ctypes.c_int64, ctypes.c_int32, vp]),
+        "rhmc_hess_random": (ctypes.c_int, [vp, P(RhmcParams), P(HessOpts), vp, vp, vp,
+                                            ctypes.c_int64, ctypes.c_int32, vp, vp, vp, vp, vp]),
+        "rhmc_hess_random_device": (ctypes.c_int, [vp, P(RhmcParams), P(HessOpts), vp, vp, vp,
+                                                   ctypes.c_int64, ctypes.c_int32, vp, vp, vp, vp,
+                                                   vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -630,6 +647,75 @@ class Context:
                                             vp(q_ptr), vp(p_ptr), vp(steps_ptr), int(n_chains),
                                             int(K), vp(status_ptr or 0), vp(trace_ptr or 0),
                                             vp(stream or 0)))
+
+    def hess_derivs(self, params, q, V=False):
+        """RHMC_efficient_computation's derivative sets (rhmc_hess_derivs) at q
+        [n_chains, 3K] or [3K]: (dVdq, dVdqq, dVdqqq), each shaped like q, with
+        V=True also V = -sum(D ln Lambda - Lambda) per chain.  No wall check."""
+        q2 = _f64(q, "q")
+        single = q2.ndim == 1
+        q2 = q2.reshape(1, -1) if single else q2.reshape(-1, q2.shape[-1])
+        n, K = q2.shape[0], q2.shape[1] // 3
+        d1, d2, d3 = np.empty_like(q2), np.empty_like(q2), np.empty_like(q2)
+        Vv = np.empty(n) if V else None
+        vp = ctypes.c_void_p
+        _check(_lib.rhmc_hess_derivs(self._h, ctypes.byref(params), vp(q2.ctypes.data),
+                                     vp(d1.ctypes.data), vp(d2.ctypes.data), vp(d3.ctypes.data),
+                                     None if Vv is None else vp(Vv.ctypes.data), n, K))
+        if single:
+            d1, d2, d3 = d1[0], d2[0], d3[0]
+            Vv = None if Vv is None else Vv[0]
+        return (d1, d2, d3, Vv) if V else (d1, d2, d3)
+
+    def hess_derivs_device(self, params, q_ptr, n_chains, K, dVdq_ptr=None, dVdqq_ptr=None,
+                           dVdqqq_ptr=None, V_ptr=None, stream=None):
+        """Device-pointer rhmc_hess_derivs (asynchronous on `stream`)."""
+        vp = ctypes.c_void_p
+        _check(_lib.rhmc_hess_derivs_device(self._h, ctypes.byref(params), vp(q_ptr),
+                                            vp(dVdq_ptr or 0), vp(dVdqq_ptr or 0),
+                                            vp(dVdqqq_ptr or 0), vp(V_ptr or 0), int(n_chains),
+                                            int(K), vp(stream or 0)))
+
+    def hess_random(self, params, dt_f, dt_xy, q, p, steps, derivs=False):
+        """samplers.RHMC_random trajectories (rhmc_hess_random): leapfrog under
+        the metric diag(dVdqq) with the steps (dt_f, dt_xy, dt_xy) per star,
+        steps[c] >= 1 steps for chain c, the flux wall at params.f_lim >= 0.
+        Returns (q, p, status, steps_done): the end state, p_half as the
+        reference leaves it, the RHMC_STATUS_* words and the completed steps
+        (below steps[c] iff the trajectory broke off); with derivs=True also
+        (dVdq, dVdqq, dVdqqq) at the end state."""
+        q2 = np.array(q, dtype=np.float64, order="C", copy=True)
+        p2 = np.array(p, dtype=np.float64, order="C", copy=True)
+        single = q2.ndim == 1
+        q2 = q2.reshape(1, -1) if single else q2.reshape(-1, q2.shape[-1])
+        p2 = p2.reshape(q2.shape)
+        n_ch, K = q2.shape[0], q2.shape[1] // 3
+        st = np.zeros(n_ch, np.int32)
+        done = np.zeros(n_ch, np.int32)
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(steps, np.int32), (n_ch,)))
+        d = [np.empty_like(q2) for _ in range(3)] if derivs else [None] * 3
+        opts = HessOpts(float(dt_f), float(dt_xy), (ctypes.c_int32 * 2)(0, 0))
+        vp = ctypes.c_void_p
+        _check(_lib.rhmc_hess_random(self._h, ctypes.byref(params), ctypes.byref(opts),
+                                     vp(q2.ctypes.data), vp(p2.ctypes.data), vp(n.ctypes.data),
+                                     n_ch, K, vp(st.ctypes.data), vp(done.ctypes.data),
+                                     *[None if a is None else vp(a.ctypes.data) for a in d]))
+        if single:
+            q2, p2, st, done = q2[0], p2[0], st[0], done[0]
+            d = [None if a is None else a[0] for a in d]
+        return (q2, p2, st, done) + (tuple(d) if derivs else ())
+
+    def hess_random_device(self, params, dt_f, dt_xy, q_ptr, p_ptr, steps_ptr, n_chains, K,
+                           status_ptr=None, steps_done_ptr=None, dVdq_ptr=None, dVdqq_ptr=None,
+                           dVdqqq_ptr=None, stream=None):
+        """Device-pointer rhmc_hess_random (asynchronous on `stream`)."""
+        opts = HessOpts(float(dt_f), float(dt_xy), (ctypes.c_int32 * 2)(0, 0))
+        vp = ctypes.c_void_p
+        _check(_lib.rhmc_hess_random_device(self._h, ctypes.byref(params), ctypes.byref(opts),
+                                            vp(q_ptr), vp(p_ptr), vp(steps_ptr), int(n_chains),
+                                            int(K), vp(status_ptr or 0), vp(steps_done_ptr or 0),
+                                            vp(dVdq_ptr or 0), vp(dVdqq_ptr or 0),
+                                            vp(dVdqqq_ptr or 0), vp(stream or 0)))
 
     def find_peaks(self, params, opts, q):
         """find_peaks' seed descent (rhmc_find_peaks) on seeds q [n, 3] =

@@ -1,8 +1,9 @@
 """The reference's older `samplers` API, routed to the MI355X engine:
 `lightsource_gym` with its three-stage pipeline — `find_peaks` (seed stars),
 `HMC_find_best_dt` (the step vector: the default branch and the step-size
-search) and unit-mass HMC (`HMC_random`) — and its own Riemannian sampler,
-`RHMC_random_diag` (leapfrog under the flux-dependent diagonal mass matrix).
+search) and unit-mass HMC (`HMC_random`) — and its own Riemannian samplers,
+`RHMC_random_diag` (leapfrog under the flux-dependent diagonal mass matrix) and
+`RHMC_random` (the metric is the diagonal of the likelihood's Hessian).
 
 Mirrors jaekor91/HMC-stellar-toy-model `samplers.py` (file:line per method):
 same class name, attributes (set after construction, like the reference's
@@ -10,11 +11,12 @@ scripts: `gym.Nobjs`, `gym.d = 3 * Nobjs`, `gym.dt = <vector [d]>`), method
 names, argument meaning, global-NumPy-RNG draw order and results.
 
 What runs where:
-  * dVdq, V, the HMC_random and RHMC_random_diag trajectories, find_peaks'
-    gradient descent of the seeds and the trials of HMC_find_best_dt's search
-    run in librhmc.so (rhmc_gradient kind 0, rhmc_energy without the position
-    check, rhmc_hmc_random, rhmc_diag_random, rhmc_find_peaks,
-    rhmc_dt_trials).  No CPU fallback.
+  * dVdq, V, the HMC_random, RHMC_random_diag and RHMC_random trajectories,
+    RHMC_efficient_computation's derivative sets, find_peaks' gradient descent
+    of the seeds and the trials of HMC_find_best_dt's search run in librhmc.so
+    (rhmc_gradient kind 0, rhmc_energy without the position check,
+    rhmc_hmc_random, rhmc_diag_random, rhmc_hess_random, rhmc_hess_derivs,
+    rhmc_find_peaks, rhmc_dt_trials).  No CPU fallback.
   * E, K, p_sample, the MH bookkeeping, the diagonal metric's host methods
     (compute_factors, mass_matrix, F, G, dlnDetdq, dpMpdq), find_peaks' seed
     grid and its merge of near-duplicate peaks (merge_peaks), and everything
@@ -43,8 +45,19 @@ chains at once and, with one chain, draws exactly what RHMC_random_diag draws.
 factor1 is computed on first use when compute_factors() has not been called.
 With save_traj, qs comes from the kernel's trace, Vs from one batched energy
 call per iteration and Ts from the host.
-Out of scope: RHMC_random (the full Hessian metric), the GMM
-testbed and the plots.
+RHMC_random (samplers.py:930-1105) and RHMC_efficient_computation (:828-927)
+keep theirs: dVdqq is the mass matrix as it comes (negative or zero included);
+the position flags are set for every coordinate below the image side, so px
+and py of a star inside the image are negated on every step; the loop runs
+i = 0 .. Niter and draws a momentum in every pass; a rejected proposal is NOT
+restored (q_chain[i] is the trajectory's end state either way) and the
+caller's float64 q_model_0 is overwritten; the run stops at i % 100 == 0 below
+50% acceptance and leaves the later rows zero.  It serves 1 <= K <= 16 on
+square images of side 16..48 (RhmcError RHMC_ERR_UNSUPPORTED otherwise) and
+f_lim >= 0; debug=True is accepted and prints nothing.  RHMC_random_batched
+runs many chains at once; with one chain its chains equal RHMC_random's and
+only the NumPy stream's position after an early stop differs.
+Out of scope: the GMM testbed (RHMC_GMM) and the plots.
 """
 import numpy as np
 
@@ -633,6 +646,140 @@ class lightsource_gym(object):
             self.A_chain[:, i - 1, 0] = acc
             q_tmp = np.where(acc[:, None], q_new, q_initial)
             self.q_chain[:, i, :] = q_tmp
+
+    # ------------------------------------------- the Hessian-metric sampler
+    def RHMC_efficient_computation(self, q_tmp, p_tmp, debug=True, dVdqq_only=False):
+        """samplers.py:828-927 with the reference's three return shapes:
+        dVdqq [d] with dVdqq_only (no wall check); (inf, inf, inf) when a flux
+        is below f_lim; else (dqdt, dpdt, E).  The derivative sums and V come
+        from the GPU (rhmc_hess_derivs).  debug is accepted and prints
+        nothing (the reference dumps every intermediate)."""
+        q_tmp = np.asarray(q_tmp, dtype=float).reshape(-1)
+        if not dVdqq_only and (q_tmp[0::3] < self.f_lim).any():
+            return np.inf, np.inf, np.inf
+        dVdq, dVdqq, dVdqqq, V = self._context().hess_derivs(self._params(), q_tmp, V=True)
+        if dVdqq_only:
+            return dVdqq
+        with np.errstate(all="ignore"):
+            dqdt = p_tmp / dVdqq
+            dpdt = -dVdqqq * ((1. / dVdqq) - dqdt ** 2) / 2. - dVdq
+            K = np.sum((p_tmp ** 2) / dVdqq) / 2. + np.log(np.prod(dVdqq)) / 2.
+            E = K + V
+        return dqdt, dpdt, E
+
+    def _E_hess_batch(self, q, p, dVdqq, V):
+        """E of RHMC_efficient_computation per chain: inf below the wall, else
+        K + V with K's log-determinant the log of a running product."""
+        with np.errstate(all="ignore"):
+            E = np.sum(p ** 2 / dVdqq, axis=1) / 2. + np.log(np.prod(dVdqq, axis=1)) / 2. + V
+        E[(q[:, 0::3] < self.f_lim).any(axis=1)] = np.inf
+        return E
+
+    def RHMC_random(self, q_model_0=None, Nchain=1, Niter=1000, thin_rate=0, Nwarmup=0,
+                    steps_min=10, steps_max=50, f_lim=0., f_lim_default=False, dt_RHMC_xy=1.,
+                    dt_RHMC_f=0.1, debug=True):
+        """samplers.py:930-1105: leapfrog under the metric diag(dVdqq), the
+        diagonal of the likelihood's Hessian, the trajectories on the GPU
+        (rhmc_hess_random).  q_model_0 (Nobjs, 3).  Sets Nobjs, d, q_chain
+        [1, Niter+1, d], E_chain, dE_chain [1, Niter+1, 1], A_chain [1, Niter,
+        1] and R_accept.  Like the reference: the loop runs i = 0 .. Niter and
+        draws a momentum in every pass; a rejected proposal is NOT restored
+        (q_chain[i] is the trajectory's end state either way) and a float64
+        q_model_0 is overwritten with the last state; "Divergence encountered
+        at (i ,z)" is printed when a trajectory breaks off; at every i % 100 ==
+        0 the run stops when fewer than 50% were accepted so far (later rows
+        stay zero).  debug is accepted and prints nothing.  f_lim < 0 is
+        refused by the library."""
+        assert Nchain == 1  # Currently we do not support any other.
+        self.Nchain = Nchain
+        self.Niter = Niter
+        self.thin_rate = thin_rate
+        self.Nwarmup = Nwarmup
+        if q_model_0 is None:
+            print("Use found seeds for inference.")
+            q_model_0 = self.q_seed
+        q_model_0 = np.asarray(q_model_0, dtype=float)
+        self.Nobjs = q_model_0.shape[0]
+        self.d = self.Nobjs * 3
+        self._set_f_lim(f_lim, f_lim_default)
+        self._run_hess(q_model_0.reshape((1, self.d)), Niter, steps_min, steps_max, dt_RHMC_f,
+                       dt_RHMC_xy, True)
+        self.R_accept = np.sum(self.A_chain[0, :] * 100) / float(self.Niter)
+        print("Chain %d Acceptance rate: %.2f%%" % (0, self.R_accept))
+
+    def RHMC_random_batched(self, q_model_0, Niter=1000, steps_min=10, steps_max=50, f_lim=0.,
+                            f_lim_default=False, dt_RHMC_xy=1., dt_RHMC_f=0.1):
+        """RHMC_random over many independent chains at once (q_model_0
+        [Nchain, d], overwritten with the last states when it is float64); per
+        iteration, i = 0 included, the global NumPy RNG draws randn(Nchain, d),
+        and for i >= 1 randint(steps_min, steps_max, Nchain) and
+        random(Nchain).  The R_accept stop applies per chain: a stopped chain's
+        later rows stay zero and its draws are still consumed.  With one chain
+        the chains equal RHMC_random's; only the position of the NumPy stream
+        after an early stop differs (RHMC_random leaves the loop there, this
+        method draws on to Niter).  Prints nothing."""
+        self._set_f_lim(f_lim, f_lim_default)
+        q0 = np.asarray(q_model_0, dtype=float)
+        q0 = q0.reshape(1, -1) if q0.ndim == 1 else q0.reshape(q0.shape[0], -1)
+        self.Nchain, self.d = q0.shape
+        self.Nobjs = self.d // 3
+        self.Niter = Niter
+        self._run_hess(q0, Niter, steps_min, steps_max, dt_RHMC_f, dt_RHMC_xy, False)
+
+    def _run_hess(self, q_tmp, Niter, steps_min, steps_max, dt_f, dt_xy, single):
+        """The MH loop of samplers.py:978-1101 over the chains q_tmp [n, d],
+        advanced in place.  Per iteration one trajectory launch, which also
+        returns the derivative sets at its end state, and one launch for V
+        there: the end state is the next iteration's start whether or not the
+        proposal is accepted (q_initial aliases q_tmp, :982, :1031)."""
+        ctx, P = self._context(), self._params()
+        n, d = q_tmp.shape
+        self.q_chain = np.zeros((n, Niter + 1, d))
+        self.E_chain = np.zeros((n, Niter + 1, 1))
+        self.dE_chain = np.zeros((n, Niter + 1, 1))
+        self.A_chain = np.zeros((n, Niter, 1))
+        _, dVdqq, _, V = ctx.hess_derivs(P, q_tmp, V=True)
+        live = np.arange(n)             # chains the R_accept stop has not ended
+        E_previous = np.zeros(n)
+        for i in range(0, Niter + 1):
+            z = self.p_sample() if single else np.random.randn(n, d)
+            with np.errstate(all="ignore"):
+                p_tmp = z.reshape(n, d) * np.sqrt(dVdqq)                      # :985-992
+            E_initial = self._E_hess_batch(q_tmp, p_tmp, dVdqq, V)            # :998
+            if i == 0:
+                self.q_chain[:, 0, :] = q_tmp
+                self.E_chain[:, 0, 0] = E_initial
+                E_previous = E_initial
+                continue
+            steps = np.random.randint(low=steps_min, high=steps_max, size=n)  # :1013
+            if live.size == 0:          # every chain stopped: the draws alone
+                np.random.random(n)
+                continue
+            self.E_chain[live, i, 0] = E_initial[live]
+            with np.errstate(invalid="ignore"):
+                self.dE_chain[live, i, 0] = (E_initial - E_previous)[live]
+            q_new, p_new, _, done, _, dVdqq_new, _ = ctx.hess_random(
+                P, dt_f, dt_xy, q_tmp[live], p_tmp[live], steps[live], derivs=True)
+            V_new = ctx.hess_derivs(P, q_new, V=True)[3]
+            if single and done[0] < steps[0]:                                 # :1026
+                print("Divergence encountered at (%d ,%d)" % (i, done[0]))
+            E_final = self._E_hess_batch(q_new, p_new, dVdqq_new, V_new)      # :1076
+            with np.errstate(invalid="ignore"):
+                dE = E_final - E_initial[live]                                # :1081
+            E_previous = E_initial
+            lnu = np.log(np.random.random(n))[live]                           # :1083
+            with np.errstate(invalid="ignore"):
+                acc = (dE < 0) | (lnu < -dE)
+            self.A_chain[live, i - 1, 0] = acc
+            q_tmp[live] = q_new         # accepted or not: not restored (:1090-1091)
+            dVdqq[live] = dVdqq_new
+            V[live] = V_new
+            self.q_chain[live, i, :] = q_new
+            if (i % 100) == 0:                                                # :1098-1101
+                R_accept = np.sum(self.A_chain[live, :i, 0] * 100, axis=1) / float(i)
+                live = live[R_accept >= 50]
+                if single and live.size == 0:
+                    break
 
     def _run(self, q0, Niter, steps_min, steps_max):
         n, d = q0.shape

@@ -62,6 +62,12 @@
  *       diagonal mass matrix of mass_matrix / F / G / dlnDetdq / dpMpdq
  *       (:574-664); the momentum draw, E, K and the MH test (:719-823) stay on
  *       the host.
+ *   rhmc_hess_derivs / rhmc_hess_random (and their _device forms)
+ *       samplers.lightsource_gym.RHMC_random (samplers.py:930-1105): the
+ *       derivative sets dVdq, dVdqq, dVdqqq and V of
+ *       RHMC_efficient_computation (:828-927) and the trajectory under the
+ *       Hessian-diagonal metric (:1016-1067); the momentum draw, E and the MH
+ *       test stay on the host.
  *   rhmc_params
  *       the instance attributes the step reads: dt, g_xx,
  *       g_ff, g_ff2, g0, g1, g2, B_count, f_lim, mB (-> f_low),
@@ -402,6 +408,75 @@ int rhmc_diag_random(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* 
 int rhmc_diag_random_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts* opts,
                             double* d_q, double* d_p, const int32_t* d_steps, int64_t n_chains,
                             int32_t K, int32_t* d_status, double* d_trace, void* stream);
+
+/* samplers.lightsource_gym.RHMC_random (samplers.py:930-1105): the sampler
+ * whose mass matrix is the diagonal of the likelihood's Hessian, dVdqq, with
+ * the third derivatives dVdqqq in its force.  Two operations, both of one
+ * kernel family (csrc/rhmc_hess.hpp: one wave per chain over the full image),
+ * which serves 1 <= K <= 16 on square images of side 16..48 and returns
+ * RHMC_ERR_UNSUPPORTED for everything else; RHMC_OPT_KERNEL does not affect it.
+ * Only B_count, f_lim and the PSF width of P are read (no prior, no metric
+ * constants).
+ *
+ * rhmc_hess_derivs: RHMC_efficient_computation's three derivative sets
+ * (:840-903) at q [n_chains][3K], per star (f, x, y):
+ *   dVdq   = (S r1 P,       f S r1 Px,                  ...y)
+ *   dVdqq  = (S r2 P^2,     f^2 S r2 Px^2 + f S r1 Pxx, ...y)
+ *   dVdqqq = (-2 S r3 P^3, -f^3 S r3 Px^3 + 3 f^2 S r2 Px Pxx + f S r1 Pxxx, ...y)
+ * with r0 = D / Lambda, r1 = 1 - r0, r2 = r0 / Lambda, r3 = r2 / Lambda and S
+ * the sum over the whole image, and V = -S (D ln Lambda - Lambda) [n_chains].
+ * There is no wall check (the reference's dVdqq_only form).  dVdq, dVdqq,
+ * dVdqqq and V are each nullable.
+ *
+ * rhmc_hess_random: the trajectory (:1016-1067) of steps[c] >= 1 steps from
+ * (q, p), with dt = (dt_f, dt_xy, dt_xy) per star:
+ *   at a derivative set: dqdt = p / dVdqq,
+ *                        dpdt = -dVdqqq (1 / dVdqq - dqdt^2) / 2 - dVdq,
+ *                        or +inf for every coordinate when some f < f_lim
+ *   p_half = p + dt dpdt(q, p) / 2
+ *   per step: stop if E(q, p_half) == +inf; q += dt dqdt(q, p_half);
+ *             p_half += dt' dpdt(new q, p_half), dt' = dt / 2 on the last step
+ * and the reference's quirks (csrc/rhmc_traj.hpp lists them): dVdqq is used
+ * as it comes, negative or zero included; the position flags are set for every
+ * coordinate below the image side, so px and py of a star inside the image
+ * are replaced by their negatives on every step; flags are sticky per star
+ * and applied when any star of the chain sets one in that step; after a wall
+ * crossing the unflagged momenta become +-inf (NaN with a zero step) and the
+ * next step stops; there is no closing half step.  The stop test needs no
+ * logarithm per pixel because V is never +-inf while f_lim >= 0: E == +inf
+ * iff some f < f_lim, or K = S p^2 / dVdqq / 2 + ln(prod dVdqq) / 2 is +inf
+ * and every coordinate of q is finite.  THEREFORE P->f_lim < 0 IS REFUSED
+ * (RHMC_ERR_ARG) by both rhmc_hess_random entry points.
+ * q and p are updated in place: q is the end state, p is p_half as the
+ * reference leaves it.  steps_done[c] (nullable) is the number of completed
+ * steps, below steps[c] iff the trajectory stopped early.  status (nullable):
+ * RHMC_STATUS_REFLECT_F when a flux flag was set, RHMC_STATUS_REFLECT_XY when
+ * a position flag was set, RHMC_STATUS_NONFINITE for a non-finite q or p.
+ * dVdq, dVdqq, dVdqqq (each nullable) receive the derivative sets AT THE END
+ * STATE, bit for bit what rhmc_hess_derivs gives there.
+ * RHMC_ERR_ARG: NULL ctx, P, opts, steps, or q / p with n_chains > 0; a
+ * non-finite step; reserved != 0; f_lim < 0; K outside 1..1024; steps[c] < 1
+ * (host-pointer call only; the device-pointer call cannot read steps, and a
+ * chain with steps < 1 there gets the first half kick alone).  n_chains = 0
+ * is a no-op.  One thread per context, like rhmc_diag_random. */
+typedef struct rhmc_hess_opts {
+  double dt_f;         /* dt_RHMC_f (finite)  */
+  double dt_xy;        /* dt_RHMC_xy (finite) */
+  int32_t reserved[2]; /* must be 0           */
+} rhmc_hess_opts;
+int rhmc_hess_derivs(rhmc_ctx* ctx, const rhmc_params* P, const double* q, double* dVdq,
+                     double* dVdqq, double* dVdqqq, double* V, int64_t n_chains, int32_t K);
+int rhmc_hess_derivs_device(rhmc_ctx* ctx, const rhmc_params* P, const double* d_q,
+                            double* d_dVdq, double* d_dVdqq, double* d_dVdqqq, double* d_V,
+                            int64_t n_chains, int32_t K, void* stream);
+int rhmc_hess_random(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_hess_opts* opts, double* q,
+                     double* p, const int32_t* steps, int64_t n_chains, int32_t K,
+                     int32_t* status, int32_t* steps_done, double* dVdq, double* dVdqq,
+                     double* dVdqqq);
+int rhmc_hess_random_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_hess_opts* opts,
+                            double* d_q, double* d_p, const int32_t* d_steps, int64_t n_chains,
+                            int32_t K, int32_t* d_status, int32_t* d_steps_done, double* d_dVdq,
+                            double* d_dVdqq, double* d_dVdqqq, void* stream);
 
 /* Per-iteration records of rhmc_mh (all nullable; host pointers for rhmc_mh,
  * device pointers for rhmc_mh_device).  Row l holds the state at the START

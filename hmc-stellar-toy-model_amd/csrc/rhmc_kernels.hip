@@ -28,6 +28,7 @@
 #include "rhmc_mhpk.hpp"
 #include "rhmc_peaks.hpp"
 #include "rhmc_dt.hpp"
+#include "rhmc_chain.hpp"
 #include "rhmc_pixk.hpp"
 #include "rhmc_wave.hpp"
 #include "rhmc_windowed.hpp"
@@ -245,6 +246,45 @@ int check_dt(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opts* o, const d
         if (steps[r] < 0 || steps[r] > 65535)
           return fail(RHMC_ERR_ARG, "steps[" + std::to_string(r) + "] outside 0..65535");
   }
+  if (!ctx) return fail(RHMC_ERR_ARG, "ctx is NULL");
+  if (n > 0 && !ctx->d_D) return fail(RHMC_ERR_ARG, "no image uploaded");
+  return RHMC_OK;
+}
+
+// The checks the two chain entry points share (n == 0 after them: a no-op),
+// arguments before the context like check_peaks.  host_call: steps is readable.
+int check_chain(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_chain_opts* o, const double* dt,
+                const double* q, int64_t n, int32_t K, const double* z, const int32_t* steps,
+                const double* lnu, bool host_call) {
+  if (!P) return fail(RHMC_ERR_ARG, "params is NULL");
+  if (!o) return fail(RHMC_ERR_ARG, "opts is NULL");
+  if (n < 0) return fail(RHMC_ERR_ARG, "n < 0");
+  if (n > ((int64_t)1 << 31)) return fail(RHMC_ERR_ARG, "n too large (2^31 chains at most)");
+  if (K < 1 || K > kMaxK) return fail(RHMC_ERR_ARG, "K must be in [1, 1024]");
+  if (o->reserved != 0) return fail(RHMC_ERR_ARG, "opts.reserved must be 0");
+  if (o->metric != RHMC_CHAIN_UNIT && o->metric != RHMC_CHAIN_DIAG)
+    return fail(RHMC_ERR_ARG, "opts.metric must be RHMC_CHAIN_UNIT or RHMC_CHAIN_DIAG");
+  if (o->n_iter < 0) return fail(RHMC_ERR_ARG, "opts.n_iter < 0");
+  if (o->iter0 < 0) return fail(RHMC_ERR_ARG, "opts.iter0 < 0");
+  if ((int64_t)o->iter0 + o->n_iter > 0x7fffffff)
+    return fail(RHMC_ERR_ARG, "opts.iter0 + opts.n_iter exceeds 2^31 - 1");
+  if (o->metric == RHMC_CHAIN_DIAG) {
+    if (!std::isfinite(o->dt_global)) return fail(RHMC_ERR_ARG, "opts.dt_global is not finite");
+    if (!(std::isfinite(o->factor1) && o->factor1 > 0.0))
+      return fail(RHMC_ERR_ARG, "opts.factor1 must be finite and > 0");
+  } else if (!dt) {
+    return fail(RHMC_ERR_ARG, "dt is NULL (RHMC_CHAIN_UNIT)");
+  }
+  const int n_draws = (z != nullptr) + (steps != nullptr) + (lnu != nullptr);
+  if (n_draws != 0 && n_draws != 3)
+    return fail(RHMC_ERR_ARG, "z, steps and lnu: pass all three or none");
+  if (n_draws == 0 &&
+      !(o->steps_min >= 1 && o->steps_min < o->steps_max && o->steps_max <= 65536))
+    return fail(RHMC_ERR_ARG, "opts: 1 <= steps_min < steps_max <= 65536 for device draws");
+  if (n > 0 && !q) return fail(RHMC_ERR_ARG, "q is NULL");
+  if (host_call && steps)
+    for (int64_t r = 0; r < n * o->n_iter; ++r)
+      if (steps[r] < 1) return fail(RHMC_ERR_ARG, "steps[" + std::to_string(r) + "] must be >= 1");
   if (!ctx) return fail(RHMC_ERR_ARG, "ctx is NULL");
   if (n > 0 && !ctx->d_D) return fail(RHMC_ERR_ARG, "no image uploaded");
   return RHMC_OK;
@@ -948,6 +988,57 @@ int rhmc_dt_trials(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opts* opts
                    rhmc_dt_record{st.dev<double>(rdE), st.dev<int32_t>(rac), st.dev<double>(rq),
                                   st.dev<double>(rz), st.dev<int32_t>(rst), st.dev<double>(rlu)}};
     return launch_dt_trials(ctx, P, opts, k, ctx->stream);
+  });
+}
+
+int rhmc_chain_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_chain_opts* opts,
+                      const double* d_dt, double* d_q, int64_t n, int32_t K, const double* d_z,
+                      const int32_t* d_steps, const double* d_lnu, uint64_t seed,
+                      const uint64_t* d_stream_id, const rhmc_chain_record* rec, void* stream) {
+  if (int rc = check_chain(ctx, P, opts, d_dt, d_q, n, K, d_z, d_steps, d_lnu, false)) return rc;
+  if (n == 0) return RHMC_OK;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  const ChainCall k{d_dt, d_q, n, K, d_z, d_steps, d_lnu, seed, d_stream_id,
+                    rec ? *rec : rhmc_chain_record{}};
+  return opts->metric == RHMC_CHAIN_DIAG ? run_chain<true>(ctx, P, opts, k, s)
+                                         : run_chain<false>(ctx, P, opts, k, s);
+}
+
+int rhmc_chain(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_chain_opts* opts, const double* dt,
+               double* q, int64_t n, int32_t K, const double* z, const int32_t* steps,
+               const double* lnu, uint64_t seed, const uint64_t* stream_id,
+               const rhmc_chain_record* rec) {
+  if (int rc = check_chain(ctx, P, opts, dt, q, n, K, z, steps, lnu, true)) return rc;
+  if (n == 0) return RHMC_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const bool diag = opts->metric == RHMC_CHAIN_DIAG;
+  const size_t sb = (size_t)n * 3 * K * sizeof(double);
+  const size_t ni = (size_t)n * opts->n_iter, ni1 = ni + (size_t)n;
+  const rhmc_chain_record r = rec ? *rec : rhmc_chain_record{};
+  Staging st(ctx);  // an array not given has no part (NULL to the kernels)
+  const int iq = st.add(q, sb, Staging::kInOut);
+  const int idt = st.add(dt, (dt && !diag) ? (size_t)3 * K * sizeof(double) : 0, Staging::kIn);
+  const int iz = st.add(z, z ? (size_t)(opts->n_iter + 1) * sb : 0, Staging::kIn);
+  const int ist = st.add(steps, steps ? ni * sizeof(int32_t) : 0, Staging::kIn);
+  const int ilu = st.add(lnu, lnu ? ni * sizeof(double) : 0, Staging::kIn);
+  const int isi = st.add(stream_id, stream_id ? (size_t)n * sizeof(uint64_t) : 0, Staging::kIn);
+  const int rq = st.add(r.q_chain, r.q_chain ? (size_t)(opts->n_iter + 1) * sb : 0, Staging::kOut);
+  const int rE = st.add(r.E_chain, r.E_chain ? ni1 * sizeof(double) : 0, Staging::kOut);
+  const int rdE = st.add(r.dE_chain, r.dE_chain ? ni1 * sizeof(double) : 0, Staging::kOut);
+  const int rac = st.add(r.accept, r.accept ? ni * sizeof(int32_t) : 0, Staging::kOut);
+  const int rst = st.add(r.status, r.status ? ni * sizeof(int32_t) : 0, Staging::kOut);
+  const int rz = st.add(r.z, r.z ? (size_t)(opts->n_iter + 1) * sb : 0, Staging::kOut);
+  const int rsp = st.add(r.steps, r.steps ? ni * sizeof(int32_t) : 0, Staging::kOut);
+  const int rlu = st.add(r.lnu, r.lnu ? ni * sizeof(double) : 0, Staging::kOut);
+  return st.run([&] {
+    const ChainCall k{st.dev<double>(idt), st.dev<double>(iq), n, K, st.dev<double>(iz),
+                      st.dev<int32_t>(ist), st.dev<double>(ilu), seed, st.dev<uint64_t>(isi),
+                      rhmc_chain_record{st.dev<double>(rq), st.dev<double>(rE),
+                                        st.dev<double>(rdE), st.dev<int32_t>(rac),
+                                        st.dev<int32_t>(rst), st.dev<double>(rz),
+                                        st.dev<int32_t>(rsp), st.dev<double>(rlu)}};
+    return diag ? run_chain<true>(ctx, P, opts, k, ctx->stream)
+                : run_chain<false>(ctx, P, opts, k, ctx->stream);
   });
 }
 

@@ -1039,6 +1039,103 @@ int launch_diag_random(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_diag_opts
   return launch_hmc_random_t<true>(ctx, c, nullptr, d_q, d_p, d_steps, n, K, d_st, s, dg);
 }
 
+// ---------------------------------------------------------------------------
+// HMC_random's / RHMC_random_diag's whole chain (rhmc_chain.hpp)
+// ---------------------------------------------------------------------------
+
+// The arguments both entry points share; the record's members may be NULL.
+struct ChainCall {
+  const double* dt;
+  double* q;
+  int64_t n;
+  int32_t K;
+  const double* z;
+  const int32_t* steps;
+  const double* lnu;
+  uint64_t seed;
+  const uint64_t* stream_id;
+  rhmc_chain_record rec;
+};
+
+template <bool DIAG>
+int launch_chain_turn(const ChainArgs& a, hipStream_t s) {
+  // one thread per chain for few stars, one wave per chain (lanes over the
+  // coordinates) from 8 stars, like run_mh's begin / end
+  if (a.K >= 8)
+    hipLaunchKernelGGL((chain_turn_kernel<true, DIAG>), dim3((unsigned)((a.n + 3) / 4)), dim3(256),
+                       0, s, a);
+  else
+    hipLaunchKernelGGL((chain_turn_kernel<false, DIAG>), dim3((unsigned)((a.n + 255) / 256)),
+                       dim3(256), 0, s, a);
+  return launch_status();
+}
+
+// The MH loop of samplers.py:504-568 / :722-815 on device buffers
+// (check_chain has passed): V(q) once, then per iteration turn -> trajectory
+// -> V(q'), and one last turn, all queued on `s` with no host synchronisation.
+template <bool DIAG>
+int run_chain(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_chain_opts* o, const ChainCall& k,
+              hipStream_t s) {
+  Consts c;
+  int rc = make_consts(P, &c);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int64_t n = k.n;
+  const int K = k.K;
+  const size_t sb = ((size_t)n * 3 * K * sizeof(double) + 255) & ~(size_t)255;
+  const size_t eb = ((size_t)n * sizeof(double) + 255) & ~(size_t)255;
+  if ((rc = ensure_mh_scratch(ctx, 2 * sb + 4 * eb + 256))) return rc;
+  char* b = (char*)ctx->mh_scratch;
+  ChainArgs a;
+  a.q = k.q;
+  a.q_prop = (double*)b;
+  a.p = (double*)(b + sb);
+  a.V_cur = (double*)(b + 2 * sb);
+  a.V_prop = (double*)(b + 2 * sb + eb);
+  a.E0 = (double*)(b + 2 * sb + 2 * eb);
+  a.steps = (int32_t*)(b + 2 * sb + 3 * eb);
+  a.z = k.z;
+  a.h_steps = k.steps;
+  a.lnu = k.lnu;
+  a.stream_id = k.stream_id;
+  a.q_chain = k.rec.q_chain;
+  a.E_chain = k.rec.E_chain;
+  a.dE_chain = k.rec.dE_chain;
+  a.accept = k.rec.accept;
+  a.r_z = k.rec.z;
+  a.r_steps = k.rec.steps;
+  a.r_lnu = k.rec.lnu;
+  a.n = n;
+  a.seed = k.seed;
+  a.factor1 = o->factor1;
+  a.f_lim = P->f_lim;
+  a.K = K;
+  a.iter = 0;
+  a.n_iter = o->n_iter;
+  a.iter0 = o->iter0;
+  a.steps_min = o->steps_min;
+  a.steps_max = o->steps_max;
+  DiagArgs dg;
+  if (DIAG) {
+    dg.dt = o->dt_global;
+    dg.inv_f1 = 1.0 / o->factor1;
+  }
+  const int f_pos = RHMC_V_NO_POSCHECK;            // lightsource_gym.V has no support check
+  if ((rc = launch_energy(ctx, c, k.q, nullptr, a.V_cur, nullptr, n, K, f_pos, s))) return rc;
+  for (int i = 0;; ++i) {
+    a.iter = i;
+    if ((rc = launch_chain_turn<DIAG>(a, s))) return rc;
+    if (i == o->n_iter) break;
+    const int32_t* steps = k.steps ? k.steps + (int64_t)i * n : a.steps;
+    int32_t* st = k.rec.status ? k.rec.status + (int64_t)i * n : nullptr;
+    if ((rc = launch_hmc_random_t<DIAG>(ctx, c, k.dt, a.q_prop, a.p, steps, n, K, st, s, dg)))
+      return rc;
+    if ((rc = launch_energy(ctx, c, a.q_prop, nullptr, a.V_prop, nullptr, n, K, f_pos, s)))
+      return rc;
+  }
+  return RHMC_OK;
+}
+
 // RHMC_random's kernels (rhmc_hess.hpp; the entry points' checks have passed):
 // the trajectory with `o`, else the derivative sets at d_q.  One wave per
 // chain, select_hess()'s waves per workgroup and LDS bytes.

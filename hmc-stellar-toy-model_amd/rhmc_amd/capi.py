@@ -40,6 +40,8 @@ OPT_DT_LANES = 6            # dt_trials: lanes per task (0: the library's choice
 DT_GRAD_REFERENCE = 0       # rhmc_dt_opts.grad (RHMC_DT_GRAD_*, include/rhmc.h)
 DT_GRAD_FULL = 1
 TABLES_STREAM, TABLES_STREAM_POISON = 0, 1
+CHAIN_UNIT = 0              # rhmc_chain_opts.metric (RHMC_CHAIN_*, include/rhmc.h)
+CHAIN_DIAG = 1
 # RHMC_KERNEL_* values by name
 KERNELS = {"auto": 0, "generic": 1, "windowed": 2, "regwin": 3, "regwin32": 4,
            "regwin_f64": 5, "lane1": 6, "lane4": 7, "lane1_f64": 8, "pixmajor": 9,
@@ -65,7 +67,8 @@ EXPORTS = ("rhmc_abi_version", "rhmc_device_count", "rhmc_last_error",
            "rhmc_dt_trials", "rhmc_dt_trials_device",
            "rhmc_diag_random", "rhmc_diag_random_device",
            "rhmc_hess_derivs", "rhmc_hess_derivs_device",
-           "rhmc_hess_random", "rhmc_hess_random_device")
+           "rhmc_hess_random", "rhmc_hess_random_device",
+           "rhmc_chain", "rhmc_chain_device")
 ABI_VERSION = 4
 
 V_FLUX_WALL = 1       # rhmc_energy f_pos bits (include/rhmc.h)
@@ -150,6 +153,33 @@ class HessOpts(ctypes.Structure):
     """Mirror of `rhmc_hess_opts` (include/rhmc.h)."""
     _fields_ = [("dt_f", ctypes.c_double), ("dt_xy", ctypes.c_double),
                 ("reserved", ctypes.c_int32 * 2)]
+
+
+class ChainOpts(ctypes.Structure):
+    """Mirror of `rhmc_chain_opts` (include/rhmc.h)."""
+    _fields_ = [("dt_global", ctypes.c_double), ("factor1", ctypes.c_double),
+                ("metric", ctypes.c_int32), ("n_iter", ctypes.c_int32),
+                ("iter0", ctypes.c_int32), ("steps_min", ctypes.c_int32),
+                ("steps_max", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class ChainRecord(ctypes.Structure):
+    """Mirror of `rhmc_chain_record` (include/rhmc.h); all fields nullable."""
+    _fields_ = [("q_chain", ctypes.c_void_p), ("E_chain", ctypes.c_void_p),
+                ("dE_chain", ctypes.c_void_p), ("accept", ctypes.c_void_p),
+                ("status", ctypes.c_void_p), ("z", ctypes.c_void_p),
+                ("steps", ctypes.c_void_p), ("lnu", ctypes.c_void_p)]
+
+
+def make_chain_opts(metric, n_iter, dt_global=0., factor1=0., iter0=0, steps_min=10,
+                    steps_max=50):
+    """rhmc_chain's options: metric "unit" / "diag" or a CHAIN_* value, Niter,
+    RHMC_random_diag's one step and factor1, the number of the iteration before
+    the call's first and the range of the device's length draws."""
+    if isinstance(metric, str):
+        metric = {"unit": CHAIN_UNIT, "diag": CHAIN_DIAG}[metric]
+    return ChainOpts(float(dt_global), float(factor1), int(metric), int(n_iter), int(iter0),
+                     int(steps_min), int(steps_max), 0)
 
 
 def make_schedule(schedule_g_ff2=None, schedule_beta=None):
@@ -269,6 +299,12 @@ def _load():
         "rhmc_hess_random_device": (ctypes.c_int, [vp, P(RhmcParams), P(HessOpts), vp, vp, vp,
                                                    ctypes.c_int64, ctypes.c_int32, vp, vp, vp, vp,
                                                    vp, vp]),
+        "rhmc_chain": (ctypes.c_int, [vp, P(RhmcParams), P(ChainOpts), vp, vp, ctypes.c_int64,
+                                      ctypes.c_int32, vp, vp, vp, ctypes.c_uint64, vp,
+                                      P(ChainRecord)]),
+        "rhmc_chain_device": (ctypes.c_int, [vp, P(RhmcParams), P(ChainOpts), vp, vp,
+                                             ctypes.c_int64, ctypes.c_int32, vp, vp, vp,
+                                             ctypes.c_uint64, vp, P(ChainRecord), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -716,6 +752,67 @@ class Context:
                                             int(K), vp(status_ptr or 0), vp(steps_done_ptr or 0),
                                             vp(dVdq_ptr or 0), vp(dVdqq_ptr or 0),
                                             vp(dVdqqq_ptr or 0), vp(stream or 0)))
+
+    def chain(self, params, opts, q, dt=None, z=None, steps=None, lnu=None, seed=0,
+              stream_id=None, record=True):
+        """The whole MH chain of samplers.HMC_random / RHMC_random_diag
+        (rhmc_chain) on the chains q [n, 3K]; opts: make_chain_opts(...); dt
+        [3K]: HMC_random's step vector (unit metric).  Draws: z [n_iter + 1, n,
+        3K], steps [n_iter, n] and lnu [n_iter, n] (all three), or none for the
+        device's Philox draws under `seed` and stream_id [n] (None: the chain
+        index).  Returns a dict with the final q and, when record, q_chain,
+        z [n_iter + 1, n, 3K], E_chain, dE_chain [n_iter + 1, n] and accept,
+        status, steps, lnu [n_iter, n]; record may also name the members
+        wanted (the others are neither written nor copied back)."""
+        q2 = np.array(q, dtype=np.float64, order="C", copy=True)
+        q2 = q2.reshape(1, -1) if q2.ndim == 1 else q2.reshape(-1, q2.shape[-1])
+        n, d = q2.shape
+        ni = opts.n_iter
+        keep = []
+
+        def arr(a, dtype, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype).reshape(shape)
+            keep.append(a)
+            return a
+
+        def ptr(a):
+            return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+        dt = None if dt is None else arr(np.broadcast_to(np.asarray(dt, np.float64), (d,)),
+                                         np.float64, (d,))
+        z = arr(z, np.float64, (ni + 1, n, d))
+        steps = arr(steps, np.int32, (ni, n))
+        lnu = arr(lnu, np.float64, (ni, n))
+        stream_id = arr(stream_id, np.uint64, (n,))
+        out, rec = {}, None
+        if record:
+            shapes = dict(q_chain=((ni + 1, n, d), np.float64), E_chain=((ni + 1, n), np.float64),
+                          dE_chain=((ni + 1, n), np.float64), accept=((ni, n), np.int32),
+                          status=((ni, n), np.int32), z=((ni + 1, n, d), np.float64),
+                          steps=((ni, n), np.int32), lnu=((ni, n), np.float64))
+            names = list(shapes) if record is True else list(record)
+            out = {k: np.zeros(*shapes[k]) for k in names}
+            rec = ChainRecord(*[out[k].ctypes.data if k in out else None for k in shapes])
+        _check(_lib.rhmc_chain(self._h, ctypes.byref(params), ctypes.byref(opts), ptr(dt),
+                               ptr(q2), n, d // 3, ptr(z), ptr(steps), ptr(lnu),
+                               ctypes.c_uint64(int(seed)), ptr(stream_id),
+                               None if rec is None else ctypes.byref(rec)))
+        del keep
+        out["q"] = q2
+        return out
+
+    def chain_device(self, params, opts, q_ptr, n, K, dt_ptr=None, z_ptr=None, steps_ptr=None,
+                     lnu_ptr=None, seed=0, stream_id_ptr=None, record=None, stream=None):
+        """Device-pointer rhmc_chain (asynchronous on `stream`); record: a
+        ChainRecord of device pointers or None."""
+        vp = ctypes.c_void_p
+        _check(_lib.rhmc_chain_device(
+            self._h, ctypes.byref(params), ctypes.byref(opts), vp(dt_ptr or 0), vp(q_ptr), int(n),
+            int(K), vp(z_ptr or 0), vp(steps_ptr or 0), vp(lnu_ptr or 0),
+            ctypes.c_uint64(int(seed)), vp(stream_id_ptr or 0),
+            None if record is None else ctypes.byref(record), vp(stream or 0)))
 
     def find_peaks(self, params, opts, q):
         """find_peaks' seed descent (rhmc_find_peaks) on seeds q [n, 3] =

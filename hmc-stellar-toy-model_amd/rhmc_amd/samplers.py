@@ -17,6 +17,14 @@ What runs where:
     (rhmc_gradient kind 0, rhmc_energy without the position check,
     rhmc_hmc_random, rhmc_diag_random, rhmc_hess_random, rhmc_hess_derivs,
     rhmc_find_peaks, rhmc_dt_trials).  No CPU fallback.
+  * With engine="device", HMC_random_batched and RHMC_random_diag_batched run
+    the whole MH chain — the momentum draw, E, the trajectories and the accept
+    test — in one rhmc_chain call with no host round trip per iteration:
+    rng="numpy" pre-draws from the global NumPy stream in the host loop's order
+    (the stream ends where the host engine leaves it), rng="philox" draws on
+    the device under `seed` and `stream_ids` and touches no NumPy stream.
+    engine="host" (the default) is the NumPy loop below; RHMC_random stays on
+    it (no restore on reject, the i % 100 stop), and so does save_traj.
   * E, K, p_sample, the MH bookkeeping, the diagonal metric's host methods
     (compute_factors, mass_matrix, F, G, dlnDetdq, dpMpdq), find_peaks' seed
     grid and its merge of near-duplicate peaks (merge_peaks), and everything
@@ -469,17 +477,66 @@ class lightsource_gym(object):
               % (0, np.sum(self.A_chain[0, :] * 100) / float(self.Niter)))
 
     def HMC_random_batched(self, q_model_0, Niter=1000, steps_min=10, steps_max=50, f_lim=0.,
-                           f_lim_default=False):
+                           f_lim_default=False, engine="host", rng="numpy", seed=0,
+                           stream_ids=None):
         """HMC_random over many independent chains at once (q_model_0
         [Nchain, d]); per iteration the global NumPy RNG draws randn(Nchain, d),
         randint(steps_min, steps_max, Nchain) and random(Nchain) — with one
-        chain exactly the reference's draws."""
+        chain exactly the reference's draws.  engine="device" runs the whole
+        loop in one rhmc_chain call: rng="numpy" on the same draws, taken from
+        the global stream in the same order before the call; rng="philox" on
+        the device's draws under `seed`, chain c on the stream stream_ids[c]
+        (None: c), which touch no NumPy stream."""
         assert self.d is not None
+        self._check_engine(engine, rng)
         self._set_f_lim(f_lim, f_lim_default)
         q0 = np.asarray(q_model_0, dtype=float).reshape(-1, self.d)
         self.Nchain = q0.shape[0]
         self.Niter = Niter
-        self._run(q0, Niter, steps_min, steps_max)
+        if engine == "device":
+            self._run_device(q0, Niter, steps_min, steps_max, "unit", 0., rng, seed, stream_ids)
+        else:
+            self._run(q0, Niter, steps_min, steps_max)
+
+    @staticmethod
+    def _check_engine(engine, rng):
+        if engine not in ("host", "device"):
+            raise ValueError("engine must be \"host\" or \"device\"")
+        if rng not in ("numpy", "philox"):
+            raise ValueError("rng must be \"numpy\" or \"philox\"")
+        if engine == "host" and rng == "philox":
+            raise ValueError("rng=\"philox\" draws on the device: it needs engine=\"device\"")
+
+    def _run_device(self, q0, Niter, steps_min, steps_max, metric, dt_global, rng, seed,
+                    stream_ids):
+        """The MH loop of _run (metric "unit") or _run_diag ("diag") in one
+        rhmc_chain call, its iteration-major records transposed into the
+        reference's [Nchain, Niter(+1), .] shapes."""
+        ctx, P = self._context(), self._params()
+        n, d = q0.shape
+        z = steps = lnu = None
+        if rng == "numpy":                                    # the host loop's order
+            z = np.empty((Niter + 1, n, d))
+            steps = np.empty((Niter, n), np.int32)
+            lnu = np.empty((Niter, n))
+            z[0] = np.random.randn(n, d)
+            for i in range(Niter):
+                z[i + 1] = np.random.randn(n, d)
+                steps[i] = np.random.randint(low=steps_min, high=steps_max, size=n)
+                lnu[i] = np.log(np.random.random(n))
+        diag = metric == "diag"
+        opts = capi.make_chain_opts(metric, Niter, dt_global=dt_global,
+                                    factor1=self.factor1 if diag else 0., steps_min=steps_min,
+                                    steps_max=steps_max)
+        dt = None if diag else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(self.dt, np.float64), (d,)))
+        out = ctx.chain(P, opts, q0, dt=dt, z=z, steps=steps, lnu=lnu, seed=seed,
+                        stream_id=None if rng == "numpy" else stream_ids,
+                        record=("q_chain", "E_chain", "dE_chain", "accept"))
+        self.q_chain = np.ascontiguousarray(np.transpose(out["q_chain"], (1, 0, 2)))
+        self.E_chain = np.ascontiguousarray(out["E_chain"].T)[:, :, None]
+        self.dE_chain = np.ascontiguousarray(out["dE_chain"].T)[:, :, None]
+        self.A_chain = np.ascontiguousarray(out["accept"].T).astype(float)[:, :, None]
 
     def _E_batch(self, q, p):
         V = self._context().energy(self._params(), q, None, f_pos=False, pos_check=False)[0]
@@ -582,18 +639,27 @@ class lightsource_gym(object):
               % (0, np.sum(self.A_chain[0, :] * 100) / float(self.Niter)))
 
     def RHMC_random_diag_batched(self, q_model_0, Niter=1000, steps_min=10, steps_max=50,
-                                 f_lim=0., f_lim_default=False, dt_global=1e-2):
+                                 f_lim=0., f_lim_default=False, dt_global=1e-2, engine="host",
+                                 rng="numpy", seed=0, stream_ids=None):
         """RHMC_random_diag over many independent chains at once (q_model_0
         [Nchain, d]); per iteration the global NumPy RNG draws randn(Nchain, d),
         randint(steps_min, steps_max, Nchain) and random(Nchain) — with one
-        chain exactly the reference's draws."""
+        chain exactly the reference's draws.  engine / rng / seed / stream_ids
+        as in HMC_random_batched."""
+        self._check_engine(engine, rng)
         self._set_f_lim(f_lim, f_lim_default)
         q0 = np.asarray(q_model_0, dtype=float)
         q0 = q0.reshape(1, -1) if q0.ndim == 1 else q0.reshape(q0.shape[0], -1)
         self.Nchain, self.d = q0.shape
         self.Nobjs = self.d // 3
         self.Niter = Niter
-        self._run_diag(q0, Niter, steps_min, steps_max, dt_global, False)
+        if engine == "device":
+            if getattr(self, "factor1", None) is None:
+                self.compute_factors()
+            self._run_device(q0, Niter, steps_min, steps_max, "diag", dt_global, rng, seed,
+                             stream_ids)
+        else:
+            self._run_diag(q0, Niter, steps_min, steps_max, dt_global, False)
 
     def _run_diag(self, q0, Niter, steps_min, steps_max, dt_global, save_traj):
         if getattr(self, "factor1", None) is None:

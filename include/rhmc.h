@@ -661,6 +661,95 @@ int rhmc_dt_trials_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_dt_opt
                           const double* d_lnu, uint64_t seed, const uint64_t* d_stream_id,
                           int32_t* d_n_accept, const rhmc_dt_record* rec, void* stream);
 
+/*
+ * The whole Metropolis-Hastings chain of samplers.lightsource_gym.HMC_random
+ * (RHMC_CHAIN_UNIT, samplers.py:460-572) or RHMC_random_diag (RHMC_CHAIN_DIAG,
+ * :668-825) on the device: n independent chains of K stars, opts->n_iter
+ * iterations, everything queued on one stream with no host round trip (per
+ * iteration one launch for the decision and the next draw, one for the
+ * trajectories, one for V).  q [n][3K] is updated in place to the last state.
+ *
+ * Row 0 (:507-513, :725-731): p = z[0] sqrt(M(q)), E_chain[0] = E(q, p),
+ * dE_chain[0] = 0, q_chain[0] = q.  Iteration i = 1 .. n_iter (:516-568,
+ * :738-817):
+ *   p = z[i] sqrt(M(q))             UNIT: M = 1, p = z[i]; DIAG: M = (1/f,
+ *                                   f factor1, f factor1) per star (:574-590)
+ *   E_initial = E(q, p)             E_chain[i]; dE_chain[i] = E_chain[i] -
+ *                                   E_chain[i-1] (:526, :751)
+ *   (q', p') = the trajectory of rhmc_hmc_random (UNIT, step vector dt [3K]) or
+ *              rhmc_diag_random (DIAG, the one step dt_global) from (q, p),
+ *              steps[i][c] steps long, with their quirks: the sticky flip mask,
+ *              and p' = p as it went in when the last step flipped (:549-554)
+ *   E_final = E(q', p')             DIAG: with M(q') (:803-804)
+ *   dE = E_final - E_initial; the chain accepts iff dE < 0 or lnu[i] < -dE
+ *   (:563, :810), then q = q'; otherwise q stays.  q_chain[i] = q.
+ * E(q, p) (:1152-1161) is +inf when any flux is below P->f_lim (:1157-1159),
+ * else V(q) + K(p): V is what rhmc_energy gives with f_pos = RHMC_V_NO_POSCHECK
+ * (no prior, no wall, no position check); UNIT: K = sum(p^2)/2 (:1171); DIAG:
+ * K = (sum(p^2/M) + log|prod M|)/2 (:1173), the product a running product in
+ * index order like np.prod, so that an overflowing product behaves as the
+ * reference's does.  NaN compares false everywhere: a NaN chain rejects for
+ * ever.  V of the current state is carried from the last accepted proposal,
+ * not recomputed (the engine's V of a chain does not depend on its batch).
+ *
+ * Draws: z [n_iter+1][n][3K] standard normals (row 0: p_initial), steps
+ * [n_iter][n] and lnu [n_iter][n] = log(u) from the host, all three or none
+ * (row i - 1 of steps and lnu belongs to iteration i).  With none the device
+ * draws them with Philox-4x32-10 under key `seed`, counter (draw, iter0 + i,
+ * stream_id[c]): draw j/2 is the Box-Muller pair of normal j, 0x80000001 the
+ * length, uniform on [steps_min, steps_max), 0x80000000 u in (0, 1]; stream_id
+ * NULL means the chain index c.  A chain's result depends on nothing but its
+ * own start, seed, stream_id[c] and iter0 — not on n, its position or its
+ * batch-mates — so a long run can be recorded in pieces (iter0 = the number of
+ * the iteration before this call's first; row 0 of a later piece is then drawn
+ * with the counter of the piece before's last iteration and its E_chain[0] is
+ * not the run's) and a sharded run can pass global chain numbers.
+ *
+ * rec (nullable, every member nullable) is iteration-major like
+ * rhmc_mh_record; status holds the trajectories' RHMC_STATUS_* words, z, steps
+ * and lnu the draws used.
+ * RHMC_ERR_ARG, all checked before any device call: NULL ctx, P or opts; NULL
+ * q with n > 0; NULL dt for UNIT; only some of z / steps / lnu; an unknown
+ * metric; n_iter < 0 or iter0 < 0; reserved != 0; DIAG: a non-finite dt_global
+ * or a factor1 that is non-finite or <= 0; device draws: steps_min / steps_max
+ * outside 1 <= steps_min < steps_max <= 65536; host entry point with host
+ * draws: any steps < 1; K outside 1..1024; n < 0 or n > 2^31.  n = 0 is a
+ * no-op; n_iter = 0 writes row 0 only.  One thread per context, like
+ * rhmc_diag_random.
+ */
+enum { RHMC_CHAIN_UNIT = 0,   /* HMC_random, samplers.py:460-572       */
+       RHMC_CHAIN_DIAG = 1 }; /* RHMC_random_diag, samplers.py:668-825 */
+typedef struct rhmc_chain_opts {
+  double dt_global;    /* DIAG: the one step (finite); UNIT: ignored           */
+  double factor1;      /* DIAG: F(f) = f factor1 (finite, > 0); UNIT: ignored  */
+  int32_t metric;      /* RHMC_CHAIN_*                                         */
+  int32_t n_iter;      /* Niter >= 0                                           */
+  int32_t iter0;       /* >= 0: number of the iteration before this call's first */
+  int32_t steps_min;   /* device draws: lengths uniform on [steps_min, steps_max), */
+  int32_t steps_max;   /*   1 <= steps_min < steps_max <= 65536                */
+  int32_t reserved;    /* must be 0                                            */
+} rhmc_chain_opts;
+typedef struct rhmc_chain_record {   /* every member nullable */
+  double* q_chain;     /* [n_iter+1][n][3K] row 0 the start, row i the state after iteration i */
+  double* E_chain;     /* [n_iter+1][n] E(start of iteration i, its momentum); row 0: E(q0, p_initial) */
+  double* dE_chain;    /* [n_iter+1][n] row 0 = 0, row i = E_chain[i] - E_chain[i-1] */
+  int32_t* accept;     /* [n_iter][n]                                          */
+  int32_t* status;     /* [n_iter][n] the trajectory's status word             */
+  double* z;           /* [n_iter+1][n][3K] the normals used                   */
+  int32_t* steps;      /* [n_iter][n] the lengths used                         */
+  double* lnu;         /* [n_iter][n]                                          */
+} rhmc_chain_record;
+int rhmc_chain(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_chain_opts* opts, const double* dt,
+               double* q, int64_t n, int32_t K, const double* z, const int32_t* steps,
+               const double* lnu, uint64_t seed, const uint64_t* stream_id,
+               const rhmc_chain_record* rec);
+/* Device pointers (rec itself is a host struct of device pointers),
+ * asynchronous on `stream`. */
+int rhmc_chain_device(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_chain_opts* opts,
+                      const double* d_dt, double* d_q, int64_t n, int32_t K, const double* d_z,
+                      const int32_t* d_steps, const double* d_lnu, uint64_t seed,
+                      const uint64_t* d_stream_id, const rhmc_chain_record* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,23 @@
 // Built and run by tests/test_traj_bodies.py and tests/test_integrate_bodies.py.
 //   traj_bodies [integrate] sweep                                  the distinct keys
 //   traj_bodies [integrate] side K img_f32 kernel n_chains [...]   one key per group of five
+//
+// With the leading word `step`, the implicit generalized-leapfrog step
+// (rhmc_leapfrog, Op::Step), whose body also depends on the chain count (the
+// lane-group kernel by kLaneChains*, kr_window_split), on
+// RHMC_OPT_WINDOW_SPLIT and on the PSF width (the 32-px one-star window by
+// rule).  step_key() follows launch_leapfrog (launch_tiledr, launch_tiledl,
+// launch_multi, launch_kr_t, launch_leap_slotted, launch_lds_image):
+//   regwin1/IMG/WIN/DT            leapfrog_k1_tiledr<IMG, WIN, DT>
+//   lane/IMG/DT/LPC               leapfrog_k1_tiledl<IMG, 28, DT, LPC>
+//   pixmajor/IMG                  leapfrog_pk<IMG, 10, IMPLICIT>
+//   multiwin/DT/1/tab             leapfrog_kr<DT, 1, true, IMPLICIT, 1>
+//   multiwin/DT/SLOTS/notab/WS    leapfrog_kr<DT, SLOTS, false, IMPLICIT, WS>
+//   ldsimage/MAXK                 leapfrog_kernel<MAXK>
+//   slotted/POLICY/SLOTS          leapfrog_win_kernel<G, SLOTS>
+// Built and run by tests/test_step_bodies.py.
+//   traj_bodies step sweep                                                    the distinct keys
+//   traj_bodies step side K img_f32 kernel n_chains window_split fwhm [...]   one key per seven
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -67,8 +84,93 @@ static std::string body_key(Op op, const SelectIn& s, int K, int64_t n) {
   return "slotted/WinG/1";
 }
 
+static double inv_two_sig2_of(double fwhm) {
+  const double sigma = fwhm / 2.354;
+  return 1.0 / (2.0 * sigma * sigma);
+}
+
+static std::string step_key(const SelectIn& s, int K, int64_t n, double fwhm) {
+  const Plan pl = select(s, /*use_Vc*/ false, inv_two_sig2_of(fwhm), Op::Step, K, n);
+  const std::string side = std::to_string(s.rows);
+  const char* dt = pl.f32 ? "float" : "double";
+  switch (pl.family) {
+    case Family::Unsupported: return "Unsupported";
+    case Family::RegWin1:  // with_side5, launch_tiledr: the plan's window and pixel cache
+      if (s.rows != 32 && s.rows != 48 && s.rows != 64 && s.rows != 96 && s.rows != 128)
+        return "regwin1/no-such-side";
+      if (pl.window != 28 && pl.window != 32) return "regwin1/no-such-window";
+      return "regwin1/" + side + "/" + std::to_string(pl.window) + "/" + dt;
+    case Family::Lane:  // with_side3, launch_tiledl
+      if (s.rows != 32 && s.rows != 48 && s.rows != 64) return "lane/no-such-side";
+      if (pl.lpc != 1 && pl.lpc != 4) return "lane/no-such-lpc";
+      return "lane/" + side + "/" + dt + "/" + std::to_string(pl.lpc);
+    case Family::PixMajor:  // launch_multi: with_side2
+      if (s.rows != 32 && s.rows != 48) return "pixmajor/no-such-side";
+      return "pixmajor/" + side;
+    case Family::MultiWin: {  // launch_kr, launch_kr_t: the split only without LDS tables
+      if (pl.tables) return std::string("multiwin/") + dt + "/1/tab";
+      const int ws = pl.split == 2 || pl.split == 4 ? pl.split : 1;
+      return std::string("multiwin/") + dt + (pl.slots == 1 ? "/1" : "/2") + "/notab/" +
+             std::to_string(ws);
+    }
+    case Family::LdsImage:  // launch_lds_image: the next power of two
+      return "ldsimage/" + std::to_string(K == 1 ? 1 : K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8 : 16);
+    case Family::Slotted: break;  // launch_leap_slotted: with_path
+    default: return "no-such-family";
+  }
+  if (pl.path == 32 || pl.path == 48) {  // with_slots: 1, 2, else 4
+    const int sl = win_slots(K);
+    return "slotted/Dense" + std::to_string(pl.path) + "/" + std::to_string(sl <= 2 ? sl : 4);
+  }
+  if (K >= kWinGlobalFromK) {  // with_big
+    const int sl = K <= 128 ? 2 : K <= 256 ? 4 : K <= 512 ? 8 : 16;
+    return "slotted/WinGG/" + std::to_string(sl);
+  }
+  return "slotted/WinG/1";
+}
+
+// A PSF inside (3.555, 4.06] px FWHM: reg_window_ok(32) holds, reg_window_ok(28)
+// does not, and the 32-px windows of the slotted kernels are not exact
+// (window_exact), so a shape only they could serve is unsupported by rule.
+static const double kWideFwhm = 3.8;
+
+static int step_main(int argc, char** argv, const char* prog) {
+  if (argc == 2 && !std::strcmp(argv[1], "sweep")) {
+    std::set<std::string> keys;
+    for (int side : {32, 40, 48, 64, 96, 128, 256})
+      for (int K = 1; K <= kMaxK; ++K)
+        for (int f32 = 0; f32 < 2; ++f32)
+          for (int kernel = RHMC_KERNEL_AUTO; kernel <= RHMC_KERNEL_DENSE; ++kernel)
+            for (int64_t n : {(int64_t)4, (int64_t)16384, (int64_t)65536})
+              for (int ws : {0, 1, 2, 4})
+                for (double fwhm : {3.5, kWideFwhm}) {
+                  SelectIn s = image(side, f32 != 0, kernel);
+                  s.window_split = ws;
+                  const std::string k = step_key(s, K, n, fwhm);
+                  if (k == "Unsupported" && !window_exact(inv_two_sig2_of(fwhm))) continue;
+                  keys.insert(k);
+                }
+    for (const std::string& k : keys) std::puts(k.c_str());
+    return 0;
+  }
+  if (argc < 8 || (argc - 1) % 7 != 0) {
+    std::fprintf(stderr,
+                 "usage: %s step sweep | side K img_f32 kernel n_chains window_split fwhm [...]\n",
+                 prog);
+    return 2;
+  }
+  for (int i = 1; i + 6 < argc; i += 7) {
+    SelectIn s = image(std::atoi(argv[i]), std::atoi(argv[i + 2]) != 0, std::atoi(argv[i + 3]));
+    s.window_split = std::atoi(argv[i + 5]);
+    std::puts(step_key(s, std::atoi(argv[i + 1]), std::atoll(argv[i + 4]),
+                       std::atof(argv[i + 6])).c_str());
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   const char* prog = argv[0];
+  if (argc > 1 && !std::strcmp(argv[1], "step")) return step_main(argc - 1, argv + 1, prog);
   Op op = Op::HmcRandom;
   if (argc > 1 && !std::strcmp(argv[1], "integrate")) {
     op = Op::Integrate;

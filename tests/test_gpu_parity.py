@@ -29,7 +29,24 @@ KERNEL_PATHS = ["auto", "generic", "windowed", "multiwin", "multiwin_notab", "pi
 def kernel_path(request, monkeypatch):
     """Run a test on the automatically chosen kernel, then again with every
     context it creates forced onto each kernel family (RHMC_OPT_KERNEL; a
-    family that does not serve a case leaves the automatic choice)."""
+    family that does not serve a case leaves the automatic choice, so many of
+    the thirteen runs repeat the automatic body).  Which bodies of the
+    implicit step the traj_* goldens reach this way (the keys of
+    tests/test_step_bodies.py, from tests/native/traj_bodies.cpp): on the
+    one-star goldens (32 and 48 px, fp32-exact, at most 8 chains)
+    regwin1/{32,48}/28/float automatically, regwin1/../32/float (regwin32),
+    regwin1/../28/double (regwin_f64), lane/../float/{1,4} and
+    lane/../double/1 (lane1, lane4, lane1_f64), ldsimage/1, slotted/WinG/1 and
+    slotted/Dense{32,48}/1, while pixmajor, multiwin and multiwin_notab leave
+    regwin1; on traj_c3, traj_prior and traj_vc (K = 10, 3, 5) pixmajor/{48,32}
+    automatically (traj_vc, whose pair potential the pixel-major kernel does
+    not serve: multiwin/float/1/tab), multiwin/float/1/tab,
+    multiwin/float/1/notab/4, ldsimage/{16,4,8}, slotted/WinG/1 and
+    slotted/Dense{48,32}/1, while the six one-star values leave the automatic
+    body; on traj_c5 (K = 64, 256 px) multiwin/float/2/notab/4 under eleven
+    values and slotted/WinG/1 under generic and windowed.  That is 24 of the 64
+    bodies: no fp64 cache but the forced one-star ones, no side of 64, 96 or
+    128 px, no window split but 4.  tests/test_gpu_step_bodies.py runs all 64."""
     from rhmc_amd import capi
     monkeypatch.setattr(capi, "DEFAULT_KERNEL", request.param)
     return request.param

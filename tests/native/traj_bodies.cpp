@@ -32,6 +32,30 @@
 // Built and run by tests/test_step_bodies.py.
 //   traj_bodies step sweep                                                    the distinct keys
 //   traj_bodies step side K img_f32 kernel n_chains window_split fwhm [...]   one key per seven
+//
+// With the leading word `energy`, `gradient` or `mh`: rhmc_energy (Op::Energy),
+// rhmc_gradient (Op::Gradient) and the Metropolis-Hastings loop rhmc_mh
+// (Op::MhFused, then the four-kernel loop).  The pair potential changes the
+// energy's body (one star with it leaves the register window), so use_Vc is
+// an input; rhmc_mh takes RHMC_OPT_MH_FUSED in its place.  energy_key() follows
+// launch_energy (launch_k1_w28, launch_energy_slotted, with_energy_win,
+// launch_energy_lds_image), gradient_key() launch_gradient (launch_lds_image,
+// with_path), mh_key() run_mh (launch_mh_k1, launch_mh_pk, else the loop):
+//   regwin1/IMG/DT                energy_k1_tiledr<IMG, DT>
+//   ldsimage/MAXK                 energy_kernel<MAXK>, gradient_kernel<MAXK>
+//   slotted/WinEG/1               energy_win_kernel<WinEG, 1>
+//   slotted/WinG/1                gradient_win_kernel<WinG, 1>
+//   slotted/WinGG/SLOTS           energy_ / gradient_win_kernel<WinGG, SLOTS>
+//   slotted/DenseIMG/SLOTS        energy_ / gradient_win_kernel<DenseG<IMG>, SLOTS>
+//   mh/regwin1/IMG/DT             mh_k1_tiledr<IMG, 28, DT>
+//   mh/pixmajor/IMG               mh_pk_v0<IMG, 10> and mh_pk_iter<IMG, 10>
+//   mh/loop/thread                mh_begin_kernel, mh_end_kernel
+//   mh/loop/wave                  mh_begin_wave_kernel, mh_end_wave_kernel
+// Built and run by tests/test_energy_bodies.py.
+//   traj_bodies energy|gradient sweep                                          the distinct keys
+//   traj_bodies energy|gradient side K img_f32 kernel n_chains use_Vc fwhm [...]   one per seven
+//   traj_bodies mh sweep
+//   traj_bodies mh side K img_f32 kernel n_chains mh_fused fwhm [...]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -168,9 +192,113 @@ static int step_main(int argc, char** argv, const char* prog) {
   return 0;
 }
 
+// The slotted launchers' switch (with_path; with_energy_win for the windowed
+// energy, whose one-slot policy is WinEG): `one_slot` names that policy.
+static std::string slotted_key(const Plan& pl, int K, const char* one_slot) {
+  if (pl.path == 32 || pl.path == 48) {  // with_slots: 1, 2, else 4
+    const int sl = win_slots(K);
+    return "slotted/Dense" + std::to_string(pl.path) + "/" + std::to_string(sl <= 2 ? sl : 4);
+  }
+  if (K >= kWinGlobalFromK) {  // with_big
+    const int sl = K <= 128 ? 2 : K <= 256 ? 4 : K <= 512 ? 8 : 16;
+    return "slotted/WinGG/" + std::to_string(sl);
+  }
+  return std::string("slotted/") + one_slot + "/1";
+}
+
+static std::string lds_image_key(int K) {  // launch_lds_image: the next power of two
+  return "ldsimage/" + std::to_string(K == 1 ? 1 : K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8 : 16);
+}
+
+static std::string energy_key(const SelectIn& s, int K, int64_t n, bool use_Vc, double fwhm) {
+  const Plan pl = select(s, use_Vc, inv_two_sig2_of(fwhm), Op::Energy, K, n);
+  switch (pl.family) {
+    case Family::Unsupported: return "Unsupported";
+    case Family::RegWin1:  // launch_k1_w28: with_side3, the 28-px window
+      if (s.rows != 32 && s.rows != 48 && s.rows != 64) return "regwin1/no-such-side";
+      return "regwin1/" + std::to_string(s.rows) + (pl.f32 ? "/float" : "/double");
+    case Family::Slotted:  // launch_energy_slotted: with_path, or with_energy_win
+      return slotted_key(pl, K, "WinEG");
+    default: return lds_image_key(K);  // launch_energy's default: launch_energy_lds_image
+  }
+}
+
+static std::string gradient_key(const SelectIn& s, int K, int64_t n, bool use_Vc, double fwhm) {
+  const Plan pl = select(s, use_Vc, inv_two_sig2_of(fwhm), Op::Gradient, K, n);
+  if (pl.family == Family::Unsupported) return "Unsupported";
+  if (pl.family != Family::Slotted) return lds_image_key(K);  // launch_gradient's first branch
+  return slotted_key(pl, K, "WinG");                          // with_path
+}
+
+// s.mh_fused holds RHMC_OPT_MH_FUSED; run_mh has no pair-potential argument of
+// its own here (the fused kernels do not serve it), so use_Vc is off.
+static std::string mh_key(const SelectIn& s, int K, int64_t n, double fwhm) {
+  const double its = inv_two_sig2_of(fwhm);
+  const Plan fused = select(s, /*use_Vc*/ false, its, Op::MhFused, K, n);
+  if (fused.family == Family::RegWin1) {  // launch_mh_k1: launch_k1_w28
+    if (s.rows != 32 && s.rows != 48 && s.rows != 64) return "mh/regwin1/no-such-side";
+    return "mh/regwin1/" + std::to_string(s.rows) + (fused.f32 ? "/float" : "/double");
+  }
+  if (fused.family == Family::PixMajor) {  // launch_mh_pk: with_side2
+    if (s.rows != 32 && s.rows != 48) return "mh/pixmajor/no-such-side";
+    return "mh/pixmajor/" + std::to_string(s.rows);
+  }
+  if (fused.family != Family::None) return "mh/no-such-family";
+  // the four-kernel loop: its step and its energy must have a plan
+  if (select(s, false, its, Op::Step, K, n).family == Family::Unsupported ||
+      select(s, false, its, Op::Energy, K, n).family == Family::Unsupported)
+    return "Unsupported";
+  // run_mh: `const bool wave_mh = K >= 8;` (one thread per chain below, one
+  // wave per chain from 8 stars); the switch lives there, not in rhmc_select.hpp
+  return K >= 8 ? "mh/loop/wave" : "mh/loop/thread";
+}
+
+// mode 0 energy, 1 gradient, 2 mh; `flag` is use_Vc (mh: RHMC_OPT_MH_FUSED)
+static std::string op_key(int mode, SelectIn s, int K, int64_t n, int flag, double fwhm) {
+  if (mode == 0) return energy_key(s, K, n, flag != 0, fwhm);
+  if (mode == 1) return gradient_key(s, K, n, flag != 0, fwhm);
+  s.mh_fused = flag;
+  return mh_key(s, K, n, fwhm);
+}
+
+static int op_main(int mode, int argc, char** argv, const char* prog) {
+  if (argc == 2 && !std::strcmp(argv[1], "sweep")) {
+    std::set<std::string> keys;
+    for (int side : {32, 40, 48, 64, 96, 256})
+      for (int K = 1; K <= kMaxK; ++K)
+        for (int f32 = 0; f32 < 2; ++f32)
+          for (int kernel = RHMC_KERNEL_AUTO; kernel <= RHMC_KERNEL_DENSE; ++kernel)
+            for (int64_t n : {(int64_t)4, (int64_t)65536})
+              for (int flag = 0; flag < 2; ++flag)
+                for (double fwhm : {3.5, kWideFwhm}) {
+                  const std::string k =
+                      op_key(mode, image(side, f32 != 0, kernel), K, n, flag, fwhm);
+                  if (k == "Unsupported" && !window_exact(inv_two_sig2_of(fwhm))) continue;
+                  keys.insert(k);
+                }
+    for (const std::string& k : keys) std::puts(k.c_str());
+    return 0;
+  }
+  if (argc < 8 || (argc - 1) % 7 != 0) {
+    std::fprintf(stderr, "usage: %s %s sweep | side K img_f32 kernel n_chains %s fwhm [...]\n",
+                 prog, mode == 0 ? "energy" : mode == 1 ? "gradient" : "mh",
+                 mode == 2 ? "mh_fused" : "use_Vc");
+    return 2;
+  }
+  for (int i = 1; i + 6 < argc; i += 7)
+    std::puts(op_key(mode, image(std::atoi(argv[i]), std::atoi(argv[i + 2]) != 0,
+                                 std::atoi(argv[i + 3])),
+                     std::atoi(argv[i + 1]), std::atoll(argv[i + 4]), std::atoi(argv[i + 5]),
+                     std::atof(argv[i + 6])).c_str());
+  return 0;
+}
+
 int main(int argc, char** argv) {
   const char* prog = argv[0];
   if (argc > 1 && !std::strcmp(argv[1], "step")) return step_main(argc - 1, argv + 1, prog);
+  for (int mode = 0; mode < 3; ++mode)
+    if (argc > 1 && !std::strcmp(argv[1], mode == 0 ? "energy" : mode == 1 ? "gradient" : "mh"))
+      return op_main(mode, argc - 1, argv + 1, prog);
   Op op = Op::HmcRandom;
   if (argc > 1 && !std::strcmp(argv[1], "integrate")) {
     op = Op::Integrate;

@@ -46,7 +46,21 @@ def kernel_path(request, monkeypatch):
     body; on traj_c5 (K = 64, 256 px) multiwin/float/2/notab/4 under eleven
     values and slotted/WinG/1 under generic and windowed.  That is 24 of the 64
     bodies: no fp64 cache but the forced one-star ones, no side of 64, 96 or
-    128 px, no window split but 4.  tests/test_gpu_step_bodies.py runs all 64."""
+    128 px, no window split but 4.  tests/test_gpu_step_bodies.py runs all 64.
+
+    Which bodies of rhmc_energy and rhmc_gradient test_gradient_and_energy
+    reaches (the keys of tests/test_energy_bodies.py, from the program's
+    `energy` and `gradient` modes; all four goldens are fp32-exact, 6 chains):
+    the energy of k1 and k1gff2 (48 px) regwin1/48/float under ten values,
+    ldsimage/1 (generic), slotted/WinEG/1 (windowed), slotted/Dense48/1
+    (dense); of k10 (48 px) ldsimage/16 under eleven values, slotted/WinEG/1
+    and slotted/Dense48/1; of vc5 (K = 5, 32 px, the pair potential)
+    ldsimage/8, slotted/WinEG/1 and slotted/Dense32/1: 7 of the 22 bodies.
+    The gradient takes ldsimage/{1,16,8}, slotted/WinG/1 (windowed) and
+    slotted/Dense{48,32}/1 (dense): 6 of the 16.  No fp64 one-star energy, no
+    side of 64 px, no ldsimage/2 or /4, nothing with two or more star slots.
+    tests/test_gpu_energy_bodies.py runs all 22 and 16, and the 8 + 2 of
+    rhmc_mh."""
     from rhmc_amd import capi
     monkeypatch.setattr(capi, "DEFAULT_KERNEL", request.param)
     return request.param

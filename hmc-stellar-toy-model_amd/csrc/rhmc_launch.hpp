@@ -1,10 +1,14 @@
 // rhmc_launch.hpp — the host side between the C-ABI (rhmc_kernels.hip) and
 // the kernels: one builder per kernel-argument struct, one launcher per
 // kernel family, and the launch_* function of every operation, which asks
-// rhmc_select.hpp for a Plan and switches on it.  Included by rhmc_kernels.hip
-// alone, after rhmc_ctx, fail() and HIP_TRY: template kernels are launched
-// from the translation unit that instantiates them.
+// rhmc_select.hpp for a Plan and picks the family's launcher.  A launcher adds
+// the launch shape (workgroup, LDS bytes, grid, table lease) and calls one
+// switch of rhmc_dispatch.hpp, which turns the plan into template arguments;
+// its functor enqueues the kernel.  No template argument is decided here.
+// Included by rhmc_kernels.hip alone, after rhmc_ctx, fail() and HIP_TRY:
+// template kernels are launched from the translation unit that instantiates them.
 #pragma once
+#include "rhmc_dispatch.hpp"
 
 namespace {
 
@@ -64,11 +68,11 @@ int ensure_mh_scratch(rhmc_ctx* ctx, size_t bytes) {
 // with 0xFF bytes ahead of the launch.
 using TableLease = std::shared_ptr<rhmc_ctx::TabBuf>;
 
-int work_tables(const rhmc_ctx* ctx, int path, int K, int64_t n, hipStream_t st,
+int work_tables(const rhmc_ctx* ctx, const Plan& pl, int K, int64_t n, hipStream_t st,
                 double** out, TableLease* lease) {
   *out = nullptr;
   lease->reset();
-  if (path != 0 || K < kWinGlobalFromK || n <= 0) return RHMC_OK;
+  if (pl.policy != Policy::WinGG || n <= 0) return RHMC_OK;
   const size_t bytes = (size_t)n * WinGG::work_doubles(K) * sizeof(double);
   const bool poison = ctx->table_mode == RHMC_TABLES_STREAM_POISON;
   std::lock_guard<std::mutex> lk(ctx->tab_mu);
@@ -212,82 +216,6 @@ void set_record(A& k, const rhmc_mh_record* rec) {
 }
 
 // ---------------------------------------------------------------------------
-// Run-time value -> template argument, each switch written once
-// ---------------------------------------------------------------------------
-template <class T> struct TypeTag { using type = T; };
-template <int N> struct IntTag { static constexpr int value = N; };
-
-// The explicit integrators (launch_integrate has checked the range).
-template <class F>
-int with_solver(int32_t solver, F&& f) {
-  if (solver == RHMC_SOLVER_HMC) return f(IntTag<RHMC_SOLVER_HMC>{});
-  if (solver == RHMC_SOLVER_RHMC_NAIVE) return f(IntTag<RHMC_SOLVER_RHMC_NAIVE>{});
-  return f(IntTag<RHMC_SOLVER_RHMC_LEAPFROG>{});
-}
-
-// Image sides: the pixel-major and dense kernels are built for 32/48 px, the
-// one-star kernels for 32/48/64, the implicit one-star step for 96/128 too.
-// The plan has checked that the side is one of them.
-template <class F>
-int with_side2(int side, F&& f) {
-  return side == 32 ? f(IntTag<32>{}) : f(IntTag<48>{});
-}
-template <class F>
-int with_side3(int side, F&& f) {
-  switch (side) {
-    case 32: return f(IntTag<32>{});
-    case 48: return f(IntTag<48>{});
-    default: return f(IntTag<64>{});
-  }
-}
-template <class F>
-int with_side5(int side, F&& f) {
-  switch (side) {
-    case 96: return f(IntTag<96>{});
-    case 128: return f(IntTag<128>{});
-    default: return with_side3(side, f);
-  }
-}
-
-// The slotted one-wave-per-chain kernels run one of two gradient policies:
-// WinG (windowed tables, any square image; needs window_exact) or DenseG<IMG>
-// (rhmc_dense.hpp, 32/48-px images: full-image pixel-major Lambda, star-major
-// sums).  A "path" names it: 0 = windowed, 32 / 48 = dense at that side.
-template <class G, class F>
-int with_slots(int K, F&& f) {
-  switch (win_slots(K)) {
-    case 1: return f(TypeTag<G>{}, IntTag<1>{});
-    case 2: return f(TypeTag<G>{}, IntTag<2>{});
-    default: return f(TypeTag<G>{}, IntTag<4>{});
-  }
-}
-// K >= kWinGlobalFromK on the windowed path: the global-table policy, two
-// slots and up (the only policy instantiated past 256 stars, 8 or 16 slots)
-static_assert(kWinGlobalFromK == 65, "below it one slot (64 stars) of LDS tables");
-template <class F>
-int with_big(int K, F&& f) {
-  if (K <= 128) return f(TypeTag<WinGG>{}, IntTag<2>{});
-  if (K <= 256) return f(TypeTag<WinGG>{}, IntTag<4>{});
-  if (K <= 512) return f(TypeTag<WinGG>{}, IntTag<8>{});
-  return f(TypeTag<WinGG>{}, IntTag<16>{});
-}
-// Windowed: LDS tables (WinG) in one slot below kWinGlobalFromK stars
-template <class F>
-int with_path(int path, int K, F&& f) {
-  if (path == 32) return with_slots<DenseG<32>>(K, f);  // dense_path: K <= 256
-  if (path == 48) return with_slots<DenseG<48>>(K, f);
-  if (K >= kWinGlobalFromK) return with_big(K, f);
-  return f(TypeTag<WinG>{}, IntTag<1>{});
-}
-// The windowed energy kernel's policy: column tables only (WinEG) below
-// kWinGlobalFromK, the global tables from there
-template <class F>
-int with_energy_win(int K, F&& f) {
-  if (K >= kWinGlobalFromK) return with_big(K, f);
-  return f(TypeTag<WinEG>{}, IntTag<1>{});
-}
-
-// ---------------------------------------------------------------------------
 // Slotted kernels: the launch shape, written once
 // ---------------------------------------------------------------------------
 struct SlotShape {
@@ -337,7 +265,7 @@ int slotted_shape(const rhmc_ctx* ctx, const Plan& pl, int K, int64_t n, hipStre
   int W;
   if (int rc = pick_waves_slotted(ctx, pl, K, &sh->lds, &W)) return rc;
   if (set_device) HIP_TRY(hipSetDevice(ctx->device));
-  if (int rc = work_tables(ctx, pl.path, K, n, s, &g->work, &sh->lease)) return rc;
+  if (int rc = work_tables(ctx, pl, K, n, s, &g->work, &sh->lease)) return rc;
   sh->grid = dim3((unsigned)((n + W - 1) / W));
   sh->block = dim3(W * kWave);
   return RHMC_OK;
@@ -346,7 +274,7 @@ int slotted_shape(const rhmc_ctx* ctx, const Plan& pl, int K, int64_t n, hipStre
 int launch_leap_slotted(const rhmc_ctx* ctx, const Plan& pl, LeapArgs a, hipStream_t s) {
   SlotShape sh;
   if (int rc = slotted_shape(ctx, pl, a.K, a.n_chains, s, false, &a.g, &sh)) return rc;
-  return with_path(pl.path, a.K, [&](auto gt, auto st) {
+  return with_policy(pl, [&](auto gt, auto st) {
     using G = typename decltype(gt)::type;
     hipLaunchKernelGGL((leapfrog_win_kernel<G, decltype(st)::value>), sh.grid, sh.block, sh.lds,
                        s, a);
@@ -357,13 +285,12 @@ int launch_leap_slotted(const rhmc_ctx* ctx, const Plan& pl, LeapArgs a, hipStre
 int launch_energy_slotted(const rhmc_ctx* ctx, const Plan& pl, EnergyArgs a, hipStream_t s) {
   SlotShape sh;
   if (int rc = slotted_shape(ctx, pl, a.K, a.n_chains, s, false, &a.g, &sh)) return rc;
-  auto go = [&](auto gt, auto st) {
+  return with_energy_policy(pl, [&](auto gt, auto st) {
     using G = typename decltype(gt)::type;
     hipLaunchKernelGGL((energy_win_kernel<G, decltype(st)::value>), sh.grid, sh.block, sh.lds, s,
                        a);
     return launch_status();
-  };
-  return pl.path ? with_path(pl.path, a.K, go) : with_energy_win(a.K, go);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -388,24 +315,24 @@ int pick_waves(const rhmc_ctx* ctx, int K, size_t* lds_bytes, int* W_out) {
                   std::to_string(ctx->max_lds) + " B); large images are not built yet");
 }
 
-// One wave per chain, MAXK register accumulators (the next power of two).
+// One wave per chain, the plan's MAXK register accumulators.
 // go(IntTag<MAXK>, grid, block, lds) enqueues the kernel.
 template <class F>
-int launch_lds_image(const rhmc_ctx* ctx, int K, int64_t n, F&& go) {
+int launch_lds_image(const rhmc_ctx* ctx, const Plan& pl, int K, int64_t n, F&& go) {
   size_t lds;
   int W;
   if (int rc = pick_waves(ctx, K, &lds, &W)) return rc;
   const dim3 grid((unsigned)((n + W - 1) / W)), block(W * kWave);
-  if (K == 1) go(IntTag<1>{}, grid, block, lds);
-  else if (K <= 2) go(IntTag<2>{}, grid, block, lds);
-  else if (K <= 4) go(IntTag<4>{}, grid, block, lds);
-  else if (K <= 8) go(IntTag<8>{}, grid, block, lds);
-  else go(IntTag<16>{}, grid, block, lds);
-  return launch_status();
+  return with_maxk(pl, [&](auto mk) {
+    go(mk, grid, block, lds);
+    return launch_status();
+  });
 }
 
-int launch_energy_lds_image(const rhmc_ctx* ctx, const EnergyArgs& a, hipStream_t s) {
-  return launch_lds_image(ctx, a.K, a.n_chains, [&](auto mk, dim3 grid, dim3 block, size_t lds) {
+int launch_energy_lds_image(const rhmc_ctx* ctx, const Plan& pl, const EnergyArgs& a,
+                            hipStream_t s) {
+  return launch_lds_image(ctx, pl, a.K, a.n_chains,
+                          [&](auto mk, dim3 grid, dim3 block, size_t lds) {
     hipLaunchKernelGGL(energy_kernel<decltype(mk)::value>, grid, block, lds, s, a);
   });
 }
@@ -436,22 +363,22 @@ int launch_tiledr_t(const rhmc_ctx* ctx, const LeapArgsK1& a, hipStream_t s) {
   hipLaunchKernelGGL((leapfrog_k1_tiledr<IMG, WIN, DT, PROF>), grid, block, lds, s, a);
   return launch_status();
 }
-// The plan's window (28 px when the PSF allows it) and pixel cache (fp32 when
-// the image allows it exactly).  A library built with -DRHMC_PHASE_PROF (make
-// prof, tools/phase_prof.py only) runs the phase-timing instantiation instead,
-// which writes cycle counts over the state.
-template <int IMG>
+// The plan's window and pixel cache (fp32 when the image allows it exactly).
+// A library built with -DRHMC_PHASE_PROF (make prof, tools/phase_prof.py only)
+// runs the phase-timing instantiation of the 28-px fp32 body instead, which
+// writes cycle counts over the state.
 int launch_tiledr(const rhmc_ctx* ctx, const Plan& pl, LeapArgsK1 a, hipStream_t s) {
-  const bool w28 = pl.window == 28;
   if (pl.f32) a.Df = ctx->d_Df;
+  return with_regwin1(pl, ctx->rows, [&](auto img, auto win, auto dt) {
+    using DT = typename decltype(dt)::type;
+    constexpr int WIN = decltype(win)::value;
 #ifdef RHMC_PHASE_PROF
-  if (w28 && pl.f32) return launch_tiledr_t<IMG, 28, float, true>(ctx, a, s);
+    constexpr bool PROF = WIN == 28 && std::is_same<DT, float>::value;
+#else
+    constexpr bool PROF = false;
 #endif
-  if (pl.f32)
-    return w28 ? launch_tiledr_t<IMG, 28, float, false>(ctx, a, s)
-               : launch_tiledr_t<IMG, 32, float, false>(ctx, a, s);
-  return w28 ? launch_tiledr_t<IMG, 28, double, false>(ctx, a, s)
-             : launch_tiledr_t<IMG, 32, double, false>(ctx, a, s);
+    return launch_tiledr_t<decltype(img)::value, WIN, DT, PROF>(ctx, a, s);
+  });
 }
 
 // Lane-group single-star kernel for large batches (rhmc_tiledl.hpp).
@@ -464,34 +391,26 @@ int launch_tiledl_t(const rhmc_ctx* ctx, const LeapArgsK1& a, hipStream_t s) {
   hipLaunchKernelGGL((leapfrog_k1_tiledl<IMG, 28, DT, LPC>), grid, block, lds, s, a);
   return launch_status();
 }
-template <int IMG>
 int launch_tiledl(const rhmc_ctx* ctx, const Plan& pl, LeapArgsK1 a, hipStream_t s) {
-  if (pl.f32) {
-    a.Df = ctx->d_Df;
-    return pl.lpc == 4 ? launch_tiledl_t<IMG, float, 4>(ctx, a, s)
-                       : launch_tiledl_t<IMG, float, 1>(ctx, a, s);
-  }
-  return pl.lpc == 4 ? launch_tiledl_t<IMG, double, 4>(ctx, a, s)
-                     : launch_tiledl_t<IMG, double, 1>(ctx, a, s);
+  if (pl.f32) a.Df = ctx->d_Df;
+  return with_lane(pl, ctx->rows, [&](auto img, auto dt, auto lpc) {
+    using DT = typename decltype(dt)::type;
+    return launch_tiledl_t<decltype(img)::value, DT, decltype(lpc)::value>(ctx, a, s);
+  });
 }
 
 // The other one-star register-window kernels (explicit integrators,
-// HMC_random, energy, fused MH): 28-px window on a 32/48/64-px image, fp32
-// pixel cache when the image is exact in fp32.  go(IntTag<IMG>, TypeTag<DT>,
-// grid, block, lds) enqueues the kernel; the caller has set Df.
+// HMC_random, energy, fused MH, find_peaks): 28-px window on a 32/48/64-px
+// image.  go(IntTag<IMG>, TypeTag<DT>, grid, block, lds) enqueues the kernel;
+// the caller has set Df.
 template <class F>
-int launch_k1_w28(const rhmc_ctx* ctx, bool f32, int64_t n, F&& go) {
-  return with_side3(ctx->rows, [&](auto img) {
-    constexpr int IMG = decltype(img)::value;
+int launch_k1_w28(const rhmc_ctx* ctx, const Plan& pl, int64_t n, F&& go) {
+  return with_k1_w28(pl, ctx->rows, [&](auto img, auto dt) {
+    using TL = TiledR<decltype(img)::value, 28, typename decltype(dt)::type>;
     dim3 grid, block;
     size_t lds;
-    if (f32) {
-      if (int rc = k1_shape<TiledR<IMG, 28, float>>(ctx, n, &grid, &block, &lds)) return rc;
-      go(img, TypeTag<float>{}, grid, block, lds);
-    } else {
-      if (int rc = k1_shape<TiledR<IMG, 28, double>>(ctx, n, &grid, &block, &lds)) return rc;
-      go(img, TypeTag<double>{}, grid, block, lds);
-    }
+    if (int rc = k1_shape<TL>(ctx, n, &grid, &block, &lds)) return rc;
+    go(img, dt, grid, block, lds);
     return launch_status();
   });
 }
@@ -515,32 +434,15 @@ int launch_kr_ws(const rhmc_ctx* ctx, const LeapArgsKR& a, int f_pos, hipStream_
   return launch_status();
 }
 
-// The window split (waves per chain pair) exists for the implicit step without
-// LDS tables only.
-template <typename DT, int SLOTS, bool TAB, int SOLVER>
-int launch_kr_t(const rhmc_ctx* ctx, const Plan& pl, const LeapArgsKR& a, int f_pos,
-                hipStream_t s) {
-  if constexpr (SOLVER == RHMC_SOLVER_IMPLICIT && !TAB) {
-    switch (pl.split) {
-      case 2: return launch_kr_ws<DT, SLOTS, TAB, SOLVER, 2>(ctx, a, f_pos, s);
-      case 4: return launch_kr_ws<DT, SLOTS, TAB, SOLVER, 4>(ctx, a, f_pos, s);
-      default: break;
-    }
-  }
-  return launch_kr_ws<DT, SLOTS, TAB, SOLVER, 1>(ctx, a, f_pos, s);
-}
-
 template <int SOLVER = RHMC_SOLVER_IMPLICIT>
 int launch_kr(const rhmc_ctx* ctx, const Plan& pl, LeapArgsKR a, int f_pos, hipStream_t s) {
   if (pl.f32) a.Df = ctx->d_Df;
-  if (pl.tables)
-    return pl.f32 ? launch_kr_t<float, 1, true, SOLVER>(ctx, pl, a, f_pos, s)
-                  : launch_kr_t<double, 1, true, SOLVER>(ctx, pl, a, f_pos, s);
-  if (pl.slots == 1)
-    return pl.f32 ? launch_kr_t<float, 1, false, SOLVER>(ctx, pl, a, f_pos, s)
-                  : launch_kr_t<double, 1, false, SOLVER>(ctx, pl, a, f_pos, s);
-  return pl.f32 ? launch_kr_t<float, 2, false, SOLVER>(ctx, pl, a, f_pos, s)
-                : launch_kr_t<double, 2, false, SOLVER>(ctx, pl, a, f_pos, s);
+  return with_multiwin<SOLVER == RHMC_SOLVER_IMPLICIT>(
+      pl, [&](auto dt, auto slots, auto tab, auto ws) {
+        using DT = typename decltype(dt)::type;
+        return launch_kr_ws<DT, decltype(slots)::value, decltype(tab)::value, SOLVER,
+                            decltype(ws)::value>(ctx, a, f_pos, s);
+      });
 }
 
 // Pixel-major multi-star kernel (rhmc_pixk.hpp), 32/48-px fp32-exact images.
@@ -589,15 +491,11 @@ int launch_leapfrog(rhmc_ctx* ctx, const rhmc_params* P, double* d_q, double* d_
   switch (pl.family) {
     case Family::RegWin1: {
       const LeapArgsK1 t = k1_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, n_steps);
-      return with_side5(ctx->rows, [&](auto img) {
-        return launch_tiledr<decltype(img)::value>(ctx, pl, t, s);
-      });
+      return launch_tiledr(ctx, pl, t, s);
     }
     case Family::Lane: {
       const LeapArgsK1 t = k1_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, n_steps);
-      return with_side3(ctx->rows, [&](auto img) {
-        return launch_tiledl<decltype(img)::value>(ctx, pl, t, s);
-      });
+      return launch_tiledl(ctx, pl, t, s);
     }
     case Family::PixMajor:
     case Family::MultiWin:
@@ -608,7 +506,8 @@ int launch_leapfrog(rhmc_ctx* ctx, const rhmc_params* P, double* d_q, double* d_
                                  leap_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, K, n_steps), s);
     default: {
       const LeapArgs a = leap_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, K, n_steps);
-      return launch_lds_image(ctx, K, n_chains, [&](auto mk, dim3 grid, dim3 block, size_t lds) {
+      return launch_lds_image(ctx, pl, K, n_chains,
+                              [&](auto mk, dim3 grid, dim3 block, size_t lds) {
         hipLaunchKernelGGL(leapfrog_kernel<decltype(mk)::value>, grid, block, lds, s, a);
       });
     }
@@ -626,14 +525,14 @@ int launch_energy(const rhmc_ctx* ctx, const Consts& c, const double* d_q, const
       if (n == 0) return RHMC_OK;
       const EnergyK1Args k{d_q, d_p, d_V, d_T, ctx->d_D, pl.f32 ? ctx->d_Df : nullptr, n, a.f_pos,
                            /*pad*/ 0, c};
-      return launch_k1_w28(ctx, pl.f32, n,
+      return launch_k1_w28(ctx, pl, n,
                            [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
         using DT = typename decltype(dt)::type;
         hipLaunchKernelGGL((energy_k1_tiledr<decltype(img)::value, DT>), grid, block, lds, s, k);
       });
     }
     case Family::Slotted: return launch_energy_slotted(ctx, pl, a, s);
-    default: return launch_energy_lds_image(ctx, a, s);
+    default: return launch_energy_lds_image(ctx, pl, a, s);
   }
 }
 
@@ -643,12 +542,12 @@ int launch_gradient(const rhmc_ctx* ctx, const Plan& pl, const Consts& c, const 
   GradArgs a{d_q, d_grad, ctx->d_D, n, K, /*with_metric*/ kind,
              make_geometry(ctx->rows, ctx->cols), c};
   if (pl.family != Family::Slotted)
-    return launch_lds_image(ctx, K, n, [&](auto mk, dim3 grid, dim3 block, size_t lds) {
+    return launch_lds_image(ctx, pl, K, n, [&](auto mk, dim3 grid, dim3 block, size_t lds) {
       hipLaunchKernelGGL(gradient_kernel<decltype(mk)::value>, grid, block, lds, s, a);
     });
   SlotShape sh;
   if (int rc = slotted_shape(ctx, pl, K, n, s, false, &a.g, &sh)) return rc;
-  return with_path(pl.path, K, [&](auto gt, auto st) {
+  return with_policy(pl, [&](auto gt, auto st) {
     using G = typename decltype(gt)::type;
     hipLaunchKernelGGL((gradient_win_kernel<G, decltype(st)::value>), sh.grid, sh.block, sh.lds,
                        s, a);
@@ -716,7 +615,7 @@ int launch_energy_ragged(rhmc_ctx* ctx, const rhmc_params* P, const double* d_q,
   EnergyArgs a = energy_args(ctx, c, d_q, nullptr, d_V, nullptr, n, K_max, f_pos);
   set_ragged(a, d_K, d_rows, ld);
   if (pl.family == Family::LdsImage)  // the pixel-major step's energy
-    return launch_energy_lds_image(ctx, a, s);
+    return launch_energy_lds_image(ctx, pl, a, s);
   return launch_energy_slotted(ctx, pl, a, s);
 }
 
@@ -742,7 +641,7 @@ bool sched_active(const rhmc_mh_schedule* sc) {
 // One star: the whole MH loop in one launch (rhmc_mhk1.hpp).
 int launch_mh_k1(const rhmc_ctx* ctx, const Plan& pl, MhK1Args k, hipStream_t s) {
   if (pl.f32) k.Df = ctx->d_Df;
-  return launch_k1_w28(ctx, pl.f32, k.n, [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
+  return launch_k1_w28(ctx, pl, k.n, [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
     using DT = typename decltype(dt)::type;
     hipLaunchKernelGGL((mh_k1_tiledr<decltype(img)::value, 28, DT>), grid, block, lds, s, k);
   });
@@ -775,6 +674,20 @@ int launch_mh_pk(const rhmc_ctx* ctx, MhKArgs k, double* V, hipStream_t s,
     HIP_TRY(hipGetLastError());
   }
   return RHMC_OK;
+}
+
+// The four-kernel loop's begin (END = false) or end of one MH iteration.
+template <bool END>
+int launch_mh_turn(const MhArgs& m, hipStream_t s) {
+  return with_mh_wave(mh_wave(m.K), [&](auto wave) {
+    constexpr bool WAVE = decltype(wave)::value;
+    const dim3 grid((unsigned)(WAVE ? (m.n + 3) / 4 : (m.n + 255) / 256)), block(256);
+    if constexpr (WAVE && END) hipLaunchKernelGGL(mh_end_wave_kernel, grid, block, 0, s, m);
+    else if constexpr (WAVE) hipLaunchKernelGGL(mh_begin_wave_kernel, grid, block, 0, s, m);
+    else if constexpr (END) hipLaunchKernelGGL(mh_end_kernel, grid, block, 0, s, m);
+    else hipLaunchKernelGGL(mh_begin_kernel, grid, block, 0, s, m);
+    return launch_status();
+  });
 }
 
 // The MH outer loop on device buffers (sampler_RHMC.py:1018-1083): per
@@ -872,10 +785,6 @@ int run_mh(rhmc_ctx* ctx, const rhmc_params* P, double* d_q, int64_t n, int32_t 
   // V reads beta through the repulsion term: a beta schedule re-evaluates
   // V(q) at each iteration's start, like the reference's V_initial (:1025)
   const bool v_sched = sched && c.use_Vc && sc->beta && sc->n_beta > 0;
-  // begin / end: one thread per chain for few stars, one wave per chain
-  // (lanes over the coordinates) from 8 stars
-  const bool wave_mh = K >= 8;
-  const dim3 grid((unsigned)(wave_mh ? (n + 3) / 4 : (n + 255) / 256)), block(256);
   for (int it = 0; it < n_iter; ++it) {
     m.iter = it;
     const rhmc_params Pl = sched ? sched_params(*P, sc, it) : *P;
@@ -885,20 +794,12 @@ int run_mh(rhmc_ctx* ctx, const rhmc_params* P, double* d_q, int64_t n, int32_t 
           (rc = launch_energy(ctx, m.c, d_q, nullptr, m.V_cur, nullptr, n, K, f_pos, s)))
         return rc;
     }
-    if (wave_mh)
-      hipLaunchKernelGGL(mh_begin_wave_kernel, grid, block, 0, s, m);
-    else
-      hipLaunchKernelGGL(mh_begin_kernel, grid, block, 0, s, m);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_mh_turn<false>(m, s))) return rc;
     if ((rc = launch_leapfrog(ctx, &Pl, m.q_prop, m.p, n, K, n_steps, nullptr, nullptr, s)))
       return rc;
     if ((rc = launch_energy(ctx, m.c, m.q_prop, nullptr, m.V_prop, nullptr, n, K, f_pos, s)))
       return rc;
-    if (wave_mh)
-      hipLaunchKernelGGL(mh_end_wave_kernel, grid, block, 0, s, m);
-    else
-      hipLaunchKernelGGL(mh_end_kernel, grid, block, 0, s, m);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_mh_turn<true>(m, s))) return rc;
   }
   return RHMC_OK;
 }
@@ -928,7 +829,7 @@ int launch_integrate(rhmc_ctx* ctx, const rhmc_params* P, int32_t solver, double
       if (pl.f32) t.Df = ctx->d_Df;
       HIP_TRY(hipSetDevice(ctx->device));
       return with_solver(solver, [&](auto sv) {
-        return launch_k1_w28(ctx, pl.f32, n,
+        return launch_k1_w28(ctx, pl, n,
                              [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
           using DT = typename decltype(dt)::type;
           hipLaunchKernelGGL(
@@ -950,7 +851,7 @@ int launch_integrate(rhmc_ctx* ctx, const rhmc_params* P, int32_t solver, double
       SlotShape sh;
       if ((rc = slotted_shape(ctx, pl, K, n, s, true, &a.g, &sh))) return rc;
       return with_solver(solver, [&](auto sv) {
-        return with_path(pl.path, K, [&](auto gt, auto st) {
+        return with_policy(pl, [&](auto gt, auto st) {
           using G = typename decltype(gt)::type;
           hipLaunchKernelGGL((integrate_win_kernel<G, decltype(sv)::value, decltype(st)::value>),
                              sh.grid, sh.block, sh.lds, s, a, fp);
@@ -976,7 +877,7 @@ int launch_hmc_random_t(rhmc_ctx* ctx, const Consts& c, const double* d_dt, doub
       LeapArgsK1 t = k1_args(ctx, c, d_q, d_p, nullptr, d_st, n, 0);
       if (pl.f32) t.Df = ctx->d_Df;
       HIP_TRY(hipSetDevice(ctx->device));
-      return launch_k1_w28(ctx, pl.f32, n,
+      return launch_k1_w28(ctx, pl, n,
                            [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
         using DT = typename decltype(dt)::type;
         if constexpr (DIAG)
@@ -998,7 +899,7 @@ int launch_hmc_random_t(rhmc_ctx* ctx, const Consts& c, const double* d_dt, doub
       LeapArgs a = leap_args(ctx, c, d_q, d_p, nullptr, d_st, n, K, 0);
       SlotShape sh;
       if ((rc = slotted_shape(ctx, pl, K, n, s, true, &a.g, &sh))) return rc;
-      return with_path(pl.path, K, [&](auto gt, auto st) {
+      return with_policy(pl, [&](auto gt, auto st) {
         using G = typename decltype(gt)::type;
         if constexpr (DIAG)
           hipLaunchKernelGGL((diag_hmc_random_win_kernel<G, decltype(st)::value>), sh.grid,
@@ -1059,15 +960,13 @@ struct ChainCall {
 
 template <bool DIAG>
 int launch_chain_turn(const ChainArgs& a, hipStream_t s) {
-  // one thread per chain for few stars, one wave per chain (lanes over the
-  // coordinates) from 8 stars, like run_mh's begin / end
-  if (a.K >= 8)
-    hipLaunchKernelGGL((chain_turn_kernel<true, DIAG>), dim3((unsigned)((a.n + 3) / 4)), dim3(256),
-                       0, s, a);
-  else
-    hipLaunchKernelGGL((chain_turn_kernel<false, DIAG>), dim3((unsigned)((a.n + 255) / 256)),
-                       dim3(256), 0, s, a);
-  return launch_status();
+  // thread or wave per chain like run_mh's begin / end (launch_mh_turn)
+  return with_mh_wave(mh_wave(a.K), [&](auto wave) {
+    constexpr bool WAVE = decltype(wave)::value;
+    const dim3 grid((unsigned)(WAVE ? (a.n + 3) / 4 : (a.n + 255) / 256)), block(256);
+    hipLaunchKernelGGL((chain_turn_kernel<WAVE, DIAG>), grid, block, 0, s, a);
+    return launch_status();
+  });
 }
 
 // The MH loop of samplers.py:504-568 / :722-815 on device buffers
@@ -1259,7 +1158,7 @@ int launch_find_peaks(rhmc_ctx* ctx, const rhmc_params* P, const rhmc_peaks_opts
     return run_peaks_stepwise(ctx, c, *o, d_q, n, d_steps, d_status, d_V, s);
   const PeaksArgs k{d_q, d_steps, d_status, d_V, ctx->d_D, pl.f32 ? ctx->d_Df : nullptr, n,
                     o->f_lim, o->dt_f_coeff, o->dt_xy_coeff, o->rel_tol, o->n_step, /*pad*/ 0, c};
-  return launch_k1_w28(ctx, pl.f32, n, [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
+  return launch_k1_w28(ctx, pl, n, [&](auto img, auto dt, dim3 grid, dim3 block, size_t lds) {
     using DT = typename decltype(dt)::type;
     hipLaunchKernelGGL((peaks_k1_tiledr<decltype(img)::value, DT>), grid, block, lds, s, k);
   });

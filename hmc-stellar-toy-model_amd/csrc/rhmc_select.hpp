@@ -1,10 +1,11 @@
 // rhmc_select.hpp — which kernel family serves a call: the one place that
 // holds the rule for (operation, K, image, PSF, batch size, RHMC_OPT_KERNEL).
 // Plain C++17 with no HIP header, so a host compiler alone builds it (and its
-// test, tests/native/select_check.cpp).  select() returns a Plan; the launchers
-// (rhmc_launch.hpp) switch on it and add only launch mechanics (workgroup,
-// LDS bytes, grid).  The operations differ on purpose; every difference is a
-// commented row of op_rules() below, nowhere else.
+// test, tests/native/select_check.cpp).  select() returns a Plan, which holds
+// every value a kernel's template arguments depend on; rhmc_dispatch.hpp turns
+// it into those arguments, and the launchers (rhmc_launch.hpp) add only launch
+// mechanics (workgroup, LDS bytes, grid).  The operations differ on purpose;
+// every difference is a commented row of op_rules() below, nowhere else.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -57,6 +58,16 @@ constexpr int win_slots(int K) {
 // pixel-major kernel stays (48 px K = 10: 2.2e8 vs 4.2e7).
 constexpr int kDenseMinK = 11;
 
+// Register accumulators of the LDS-image kernel for K stars: the next power of two.
+constexpr int lds_image_maxk(int K) {
+  return K == 1 ? 1 : K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8 : kMaxKGeneric;
+}
+
+// The MH loop's begin / end kernels and the chain turn: one thread per chain
+// for few stars, one wave per chain (lanes over the coordinates) from 8 stars.
+constexpr int kMhWaveFromK = 8;
+constexpr bool mh_wave(int K) { return K >= kMhWaveFromK; }
+
 // Lanes per chain of the lane-group kernel for a K = 1 batch of n chains, or 0
 // for the register-window kernel.
 // Measured (C2 geometry, 500 steps, chain-steps/s): 16384 chains tiledr
@@ -101,6 +112,7 @@ struct Plan {
   int path = 0;
   Policy policy = Policy::WinG;
   int slots = 1;         // Slotted, MultiWin: star slots per lane
+  int maxk = kMaxKGeneric;  // LdsImage: register accumulators (1, 2, 4, 8, 16)
   int window = 28;       // RegWin1: 28- or 32-px window
   bool f32 = false;      // RegWin1, Lane, MultiWin: fp32 pixel cache
   int lpc = 0;           // Lane: lanes per chain (1 or 4)
@@ -410,6 +422,7 @@ inline Plan select(const SelectIn& s, bool use_Vc, double inv_two_sig2, Op op, i
   }
   if (!pl.path && r.lds_image && !use_windowed(s, K)) {
     pl.family = Family::LdsImage;
+    pl.maxk = lds_image_maxk(K);
     return pl;
   }
   if (!pl.path && !window_exact(inv_two_sig2)) {

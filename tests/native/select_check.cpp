@@ -69,6 +69,15 @@ int main() {
     // ... and their energy / gradient come from the LDS-image kernels
     CHECK(plan(image(side, true), Op::Energy, 10, 4096).family == Family::LdsImage);
     CHECK(plan(image(side, true), Op::Gradient, 10, 4096).family == Family::LdsImage);
+    // ... with as many register accumulators as the next power of two of K
+    const int accumulators[][2] = {{1, 1}, {2, 2}, {3, 4}, {4, 4},
+                                   {5, 8}, {8, 8}, {9, 16}, {16, 16}};
+    for (const auto& ka : accumulators) {
+      p = plan(image(side, true, RHMC_KERNEL_GENERIC), Op::Step, ka[0], 4096);
+      CHECK(p.family == Family::LdsImage && p.maxk == ka[1]);
+      for (Op op : {Op::Energy, Op::Gradient})
+        CHECK(plan(image(side, true, RHMC_KERNEL_GENERIC), op, ka[0], 4096).maxk == ka[1]);
+    }
 
     // dense from 11 stars: B4 (K = 51) one slot, K = 100 two
     for (Op op : {Op::Step, Op::Integrate, Op::HmcRandom, Op::Energy, Op::Gradient}) {
@@ -207,6 +216,9 @@ int main() {
     p = forced(RHMC_KERNEL_LANE1, Op::Step, 10, 4096);
     CHECK(p.family == Family::PixMajor);
   }
+
+  // the MH loop's begin / end and the chain turn: a wave per chain from 8 stars
+  CHECK(!mh_wave(1) && !mh_wave(7) && mh_wave(8) && mh_wave(1024));
 
   {  // ragged families: 1 dense, 2 windowed, 3 pixel-major, 0 fixed K per launch
     const SelectIn s48 = image(48, true), s48d = image(48, false), s64 = image(64, true);

@@ -1,8 +1,9 @@
 """Which kernel body serves rhmc_energy, rhmc_gradient and rhmc_mh, on the CPU.
 
 tests/native/traj_bodies.cpp in its `energy`, `gradient` and `mh` modes (a
-host compiler and csrc/rhmc_select.hpp alone) names the body that each
-operation launches for a shape, following csrc/rhmc_launch.hpp's switches
+host compiler, csrc/rhmc_select.hpp and csrc/rhmc_dispatch.hpp alone) names the
+body that each operation launches for a shape, by calling the switches of
+rhmc_dispatch.hpp that csrc/rhmc_launch.hpp's launchers call
 (launch_energy, launch_energy_slotted, launch_energy_lds_image;
 launch_gradient; run_mh, launch_mh_k1, launch_mh_pk).  The pair potential
 changes the energy's body, so the program takes use_Vc per case; rhmc_mh takes

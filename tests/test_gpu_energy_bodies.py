@@ -8,10 +8,10 @@ four-kernel loop in its two forms (run_mh: one thread per chain below 8 stars,
 one wave per chain from 8).  TABLE_E, TABLE_G and TABLE_MH hold at least one
 shape per body with the body's key beside it; tests/test_energy_bodies.py
 checks on the CPU (tests/native/traj_bodies.cpp in its `energy`, `gradient`
-and `mh` modes, csrc/rhmc_select.hpp alone) that every shape is served by the
-body written here at every chain count launched below, and that the tables
-cover every body.  Images and starts come from test_gpu_rhmc_diag._field; no
-golden is read.
+and `mh` modes, which ask csrc/rhmc_select.hpp and the launchers' own
+csrc/rhmc_dispatch.hpp) that every shape is served by the body written here at
+every chain count launched below, and that the tables cover every body.  Images
+and starts come from test_gpu_rhmc_diag._field; no golden is read.
 
 Energy, each row against oracle.rhmc_ref.RefModel.V / .T (V at rtol 1e-12, T
 at rtol 1e-12 and atol 1e-12, the bars of test_gpu_parity):

@@ -8,8 +8,9 @@ integrate_win_kernel (windowed and dense).  TABLE takes the shapes of
 test_gpu_traj_bodies.TABLE, at least one per body with the body's key beside
 it, and adds a step size and a step count per row;
 tests/test_integrate_bodies.py checks on the CPU (tests/native/traj_bodies.cpp
-in its `integrate` mode) that every shape is served by the body written here
-and that the table covers all 25.
+in its `integrate` mode, which asks csrc/rhmc_select.hpp and the launchers' own
+csrc/rhmc_dispatch.hpp) that every shape is served by the body written here and
+that the table covers all 25.
 
 Each (row, solver) runs, against oracle.rhmc_ref.RefModel's hmc_step /
 rhmc_naive_step / rhmc_leapfrog_step stepped in Python:

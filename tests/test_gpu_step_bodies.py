@@ -3,9 +3,10 @@
 rhmc_leapfrog (Op::Step) launches one of 64 kernel bodies
 (csrc/rhmc_launch.hpp: launch_leapfrog and its helpers).  TABLE holds at least
 one shape per body with the body's key beside it; tests/test_step_bodies.py
-checks on the CPU (tests/native/traj_bodies.cpp in its `step` mode,
-csrc/rhmc_select.hpp alone) that every shape is served by the body written
-here at every chain count launched below, and that the table covers all 64.
+checks on the CPU (tests/native/traj_bodies.cpp in its `step` mode, which asks
+csrc/rhmc_select.hpp and the launchers' own csrc/rhmc_dispatch.hpp) that every
+shape is served by the body written here at every chain count launched below,
+and that the table covers all 64.
 
 Each row runs, against oracle.rhmc_ref.RefModel.step stepped in Python:
 

@@ -5,8 +5,9 @@ of 25 kernel bodies each (csrc/rhmc_launch.hpp: launch_hmc_random_t), all of
 which run random_trajectory<SLOTS, DIAG> of csrc/rhmc_traj.hpp.  TABLE holds at
 least one shape per body, with the body's key beside it;
 tests/test_traj_bodies.py checks on the CPU (tests/native/traj_bodies.cpp,
-csrc/rhmc_select.hpp alone) that every shape is served by the body written
-here and that the table covers all 25.
+which asks csrc/rhmc_select.hpp and the launchers' own
+csrc/rhmc_dispatch.hpp) that every shape is served by the body written here
+and that the table covers all 25.
 
 Each shape runs `free` (no flux wall; unequal lengths inside a wave) and
 `wall`.  The star sent into the wall is star K - 1 in even chains (the last

@@ -1,9 +1,10 @@
 """Which kernel body serves an explicit integrator, on the CPU.
 
-tests/native/traj_bodies.cpp in its `integrate` mode (a host compiler and
-csrc/rhmc_select.hpp alone) names the body that rhmc_integrate launches for a
-shape under RHMC_SOLVER_HMC, _RHMC_NAIVE or _RHMC_LEAPFROG, following
-csrc/rhmc_launch.hpp's switches (launch_integrate).  Op::Integrate shares its
+tests/native/traj_bodies.cpp in its `integrate` mode (a host compiler,
+csrc/rhmc_select.hpp and csrc/rhmc_dispatch.hpp alone) names the body that
+rhmc_integrate launches for a shape under RHMC_SOLVER_HMC, _RHMC_NAIVE or
+_RHMC_LEAPFROG, by calling the switches of rhmc_dispatch.hpp that
+launch_integrate (csrc/rhmc_launch.hpp) calls.  Op::Integrate shares its
 row of op_rules() with Op::HmcRandom, so the bodies are the 25 of
 test_traj_bodies.BODIES, each built once per solver:
 

@@ -1,9 +1,11 @@
 """Which kernel body serves a random-length trajectory, on the CPU.
 
-tests/native/traj_bodies.cpp (a host compiler and csrc/rhmc_select.hpp alone)
-names the body that rhmc_hmc_random / rhmc_diag_random launch for a shape,
-following csrc/rhmc_launch.hpp's switches.  BODIES is written from the
-instantiations those switches can reach, not from the program:
+tests/native/traj_bodies.cpp (a host compiler, csrc/rhmc_select.hpp and
+csrc/rhmc_dispatch.hpp alone) names the body that rhmc_hmc_random /
+rhmc_diag_random launch for a shape: it calls the switches of rhmc_dispatch.hpp
+that csrc/rhmc_launch.hpp's launchers call, with functors that name the
+template arguments.  BODIES is written from the instantiations those switches
+can reach, not from the program:
 
 * the sweep (sides 32/48/64/96, K = 1..1024, fp32-exact or not, every
   RHMC_KERNEL_* value, 4 and 65536 chains) yields exactly these 25 and never

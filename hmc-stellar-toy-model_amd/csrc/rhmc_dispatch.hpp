@@ -11,8 +11,9 @@
 
 namespace rhmc {
 
-// The slotted kernels' gradient policies (rhmc_windowed.hpp, rhmc_dense.hpp);
-// a tag of an incomplete type is enough for a switch.
+// The slotted kernels' gradient policies (rhmc_perwave.hpp, rhmc_windowed.hpp,
+// rhmc_dense.hpp); a tag of an incomplete type is enough for a switch.
+template <int MAXK> struct LdsG;
 struct WinG;
 struct WinEG;
 struct WinGG;
@@ -60,10 +61,31 @@ auto with_dt(const Plan& pl, F&& f) {
   return pl.f32 ? f(TypeTag<float>{}) : f(TypeTag<double>{});
 }
 
-// The slotted one-wave-per-chain kernels, f(TypeTag<G>, IntTag<SLOTS>): the
-// dense policy DenseG<32 / 48> in 1, 2 or 4 slots (dense_path: K <= 256), the
-// global-table policy WinGG in 2, 4, 8 or 16 (the only policy instantiated
-// past 256 stars), else one slot of LDS tables: G1, WinG or the energy's WinEG.
+// LDS-image plans, f(IntTag<MAXK>): the plan's register accumulators (the
+// step's leapfrog_kernel<MAXK>).
+template <class F>
+auto with_maxk(const Plan& pl, F&& f) {
+  switch (pl.maxk) {
+    case 1: return f(IntTag<1>{});
+    case 2: return f(IntTag<2>{});
+    case 4: return f(IntTag<4>{});
+    case 8: return f(IntTag<8>{});
+    default: return f(IntTag<16>{});
+  }
+}
+
+// The slotted one-wave-per-chain kernels, f(TypeTag<G>, IntTag<SLOTS>).
+// An LDS-image plan's energy and gradient: the policy LdsG<MAXK> in one slot.
+template <class F>
+auto with_lds_policy(const Plan& pl, F&& f) {
+  return with_maxk(pl, [&](auto mk) {
+    return f(TypeTag<LdsG<decltype(mk)::value>>{}, IntTag<1>{});
+  });
+}
+// A slotted plan: the dense policy DenseG<32 / 48> in 1, 2 or 4 slots
+// (dense_path: K <= 256), the global-table policy WinGG in 2, 4, 8 or 16 (the
+// only policy instantiated past 256 stars), else one slot of LDS tables: G1,
+// WinG or the energy's WinEG.
 template <class G, class F>
 auto with_dense_slots(const Plan& pl, F&& f) {
   switch (pl.slots) {
@@ -101,17 +123,15 @@ template <class F>
 auto with_energy_policy(const Plan& pl, F&& f) {
   return pl.path ? with_policy(pl, f) : with_policy_from<WinEG>(pl, f);
 }
-
-// LDS-image kernels, f(IntTag<MAXK>): the plan's register accumulators.
+// Gradient and energy, whose plan may be an LDS-image one (the slotted step,
+// the integrators and the trajectories never get one and call with_policy).
 template <class F>
-auto with_maxk(const Plan& pl, F&& f) {
-  switch (pl.maxk) {
-    case 1: return f(IntTag<1>{});
-    case 2: return f(IntTag<2>{});
-    case 4: return f(IntTag<4>{});
-    case 8: return f(IntTag<8>{});
-    default: return f(IntTag<16>{});
-  }
+auto with_perwave_policy(const Plan& pl, F&& f) {
+  return pl.family == Family::LdsImage ? with_lds_policy(pl, f) : with_policy(pl, f);
+}
+template <class F>
+auto with_perwave_energy_policy(const Plan& pl, F&& f) {
+  return pl.family == Family::LdsImage ? with_lds_policy(pl, f) : with_energy_policy(pl, f);
 }
 
 // The implicit one-star register-window step, f(IntTag<IMG>, IntTag<WIN>,

@@ -1,7 +1,8 @@
 // rhmc_kernels.hip — the main translation unit of librhmc.so: the context,
 // error reporting, option handling and the C-ABI declared in include/rhmc.h.
-// The kernels live in the rhmc_*.hpp headers (the one-wave-per-chain ones in
-// rhmc_perwave.hpp); rhmc_select.hpp chooses the kernel family of a call and
+// The kernels live in the rhmc_*.hpp headers (the one-wave-per-chain ones, the
+// slotted frame for the LDS-image, windowed and dense gradient policies and
+// the LDS-image step, in rhmc_perwave.hpp); rhmc_select.hpp chooses the kernel family of a call and
 // rhmc_launch.hpp builds its arguments and launches it.  Every kernel but the
 // two of rhmc_dense_ilp.hip is instantiated, and so launched, from this unit.
 #include <hip/hip_runtime.h>

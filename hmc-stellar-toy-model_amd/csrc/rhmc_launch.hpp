@@ -185,7 +185,7 @@ LeapArgsKR kr_args(const rhmc_ctx* ctx, const Consts& c, double* q, double* p, i
                     /*pad*/ 0, c, dtv, steps};
 }
 
-// One-wave-per-chain kernels (LDS-image, slotted).
+// One-wave-per-chain kernels (the slotted frame, the LDS-image step).
 LeapArgs leap_args(const rhmc_ctx* ctx, const Consts& c, double* q, double* p, int32_t* it,
                    int32_t* st, int64_t n, int K, int n_steps) {
   return LeapArgs{q, p, it, st, ctx->d_D, n, K, n_steps, make_geometry(ctx->rows, ctx->cols), c};
@@ -224,13 +224,24 @@ struct SlotShape {
   TableLease lease;  // held until the launch is enqueued
 };
 
-// W waves per workgroup and the LDS they need.  Windowed: LDS = W * tables
+// W waves per workgroup and the LDS they need.  LDS-image: W waves share one
+// LDS copy of D, the largest W <= 4 whose LDS fits.  Windowed: LDS = W * tables
 // (K <= 256: 136 KB for one wave, within gfx950's 160 KB; a device with less
 // LDS gets RHMC_ERR_UNSUPPORTED here, not a failed launch); WinGG: the exp
 // table only; dense: four waves (32 px: 41.5 KB, 48 px: 92.6 KB).
 int pick_waves_slotted(const rhmc_ctx* ctx, const Plan& pl, int K, size_t* lds, int* W) {
   const size_t max_lds = (size_t)ctx->max_lds;
   *W = 4;
+  if (pl.family == Family::LdsImage) {  // the bytes do not depend on MAXK
+    using L = LdsG<kMaxKGeneric>;
+    while (*W > 1 && L::lds_bytes(*W, K, ctx->rows, ctx->cols) > max_lds) *W >>= 1;
+    *lds = L::lds_bytes(*W, K, ctx->rows, ctx->cols);
+    if (*lds > max_lds)
+      return fail(RHMC_ERR_UNSUPPORTED,
+                  "image + PSF tables exceed LDS (" + std::to_string(*lds) + " B > " +
+                      std::to_string(ctx->max_lds) + " B); large images are not built yet");
+    return RHMC_OK;
+  }
   switch (pl.policy) {
     case Policy::DenseG:
       *lds = pl.path == 32 ? DenseG<32>::lds_bytes(4) : DenseG<48>::lds_bytes(4);
@@ -285,55 +296,11 @@ int launch_leap_slotted(const rhmc_ctx* ctx, const Plan& pl, LeapArgs a, hipStre
 int launch_energy_slotted(const rhmc_ctx* ctx, const Plan& pl, EnergyArgs a, hipStream_t s) {
   SlotShape sh;
   if (int rc = slotted_shape(ctx, pl, a.K, a.n_chains, s, false, &a.g, &sh)) return rc;
-  return with_energy_policy(pl, [&](auto gt, auto st) {
+  return with_perwave_energy_policy(pl, [&](auto gt, auto st) {
     using G = typename decltype(gt)::type;
     hipLaunchKernelGGL((energy_win_kernel<G, decltype(st)::value>), sh.grid, sh.block, sh.lds, s,
                        a);
     return launch_status();
-  });
-}
-
-// ---------------------------------------------------------------------------
-// LDS-image kernels
-// ---------------------------------------------------------------------------
-
-// Workgroup shape: W waves share one LDS copy of D; pick the largest W<=4
-// whose LDS fits.
-int pick_waves(const rhmc_ctx* ctx, int K, size_t* lds_bytes, int* W_out) {
-  const size_t img = (size_t)ctx->rows * ctx->cols * sizeof(double);
-  const size_t tab = table_doubles(K, ctx->rows, ctx->cols) * sizeof(double);
-  for (int W = 4; W >= 1; W >>= 1) {
-    const size_t need = img + W * tab;
-    if (need <= (size_t)ctx->max_lds) {
-      *lds_bytes = need;
-      *W_out = W;
-      return RHMC_OK;
-    }
-  }
-  return fail(RHMC_ERR_UNSUPPORTED,
-              "image + PSF tables exceed LDS (" + std::to_string(img + tab) + " B > " +
-                  std::to_string(ctx->max_lds) + " B); large images are not built yet");
-}
-
-// One wave per chain, the plan's MAXK register accumulators.
-// go(IntTag<MAXK>, grid, block, lds) enqueues the kernel.
-template <class F>
-int launch_lds_image(const rhmc_ctx* ctx, const Plan& pl, int K, int64_t n, F&& go) {
-  size_t lds;
-  int W;
-  if (int rc = pick_waves(ctx, K, &lds, &W)) return rc;
-  const dim3 grid((unsigned)((n + W - 1) / W)), block(W * kWave);
-  return with_maxk(pl, [&](auto mk) {
-    go(mk, grid, block, lds);
-    return launch_status();
-  });
-}
-
-int launch_energy_lds_image(const rhmc_ctx* ctx, const Plan& pl, const EnergyArgs& a,
-                            hipStream_t s) {
-  return launch_lds_image(ctx, pl, a.K, a.n_chains,
-                          [&](auto mk, dim3 grid, dim3 block, size_t lds) {
-    hipLaunchKernelGGL(energy_kernel<decltype(mk)::value>, grid, block, lds, s, a);
   });
 }
 
@@ -504,11 +471,13 @@ int launch_leapfrog(rhmc_ctx* ctx, const rhmc_params* P, double* d_q, double* d_
     case Family::Slotted:
       return launch_leap_slotted(ctx, pl,
                                  leap_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, K, n_steps), s);
-    default: {
-      const LeapArgs a = leap_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, K, n_steps);
-      return launch_lds_image(ctx, pl, K, n_chains,
-                              [&](auto mk, dim3 grid, dim3 block, size_t lds) {
-        hipLaunchKernelGGL(leapfrog_kernel<decltype(mk)::value>, grid, block, lds, s, a);
+    default: {  // LDS-image: leapfrog_kernel<MAXK>, the frame's launch shape
+      LeapArgs a = leap_args(ctx, c, d_q, d_p, d_it, d_st, n_chains, K, n_steps);
+      SlotShape sh;
+      if ((rc = slotted_shape(ctx, pl, K, n_chains, s, false, &a.g, &sh))) return rc;
+      return with_maxk(pl, [&](auto mk) {
+        hipLaunchKernelGGL(leapfrog_kernel<decltype(mk)::value>, sh.grid, sh.block, sh.lds, s, a);
+        return launch_status();
       });
     }
   }
@@ -531,8 +500,7 @@ int launch_energy(const rhmc_ctx* ctx, const Consts& c, const double* d_q, const
         hipLaunchKernelGGL((energy_k1_tiledr<decltype(img)::value, DT>), grid, block, lds, s, k);
       });
     }
-    case Family::Slotted: return launch_energy_slotted(ctx, pl, a, s);
-    default: return launch_energy_lds_image(ctx, pl, a, s);
+    default: return launch_energy_slotted(ctx, pl, a, s);  // slotted, LDS-image
   }
 }
 
@@ -541,13 +509,9 @@ int launch_gradient(const rhmc_ctx* ctx, const Plan& pl, const Consts& c, const 
                     double* d_grad, int64_t n, int K, int kind, hipStream_t s) {
   GradArgs a{d_q, d_grad, ctx->d_D, n, K, /*with_metric*/ kind,
              make_geometry(ctx->rows, ctx->cols), c};
-  if (pl.family != Family::Slotted)
-    return launch_lds_image(ctx, pl, K, n, [&](auto mk, dim3 grid, dim3 block, size_t lds) {
-      hipLaunchKernelGGL(gradient_kernel<decltype(mk)::value>, grid, block, lds, s, a);
-    });
   SlotShape sh;
   if (int rc = slotted_shape(ctx, pl, K, n, s, false, &a.g, &sh)) return rc;
-  return with_policy(pl, [&](auto gt, auto st) {
+  return with_perwave_policy(pl, [&](auto gt, auto st) {
     using G = typename decltype(gt)::type;
     hipLaunchKernelGGL((gradient_win_kernel<G, decltype(st)::value>), sh.grid, sh.block, sh.lds,
                        s, a);
@@ -614,9 +578,7 @@ int launch_energy_ragged(rhmc_ctx* ctx, const rhmc_params* P, const double* d_q,
   if ((rc = plan_for(ctx, c, Op::Energy, K_max, n, &pl))) return rc;
   EnergyArgs a = energy_args(ctx, c, d_q, nullptr, d_V, nullptr, n, K_max, f_pos);
   set_ragged(a, d_K, d_rows, ld);
-  if (pl.family == Family::LdsImage)  // the pixel-major step's energy
-    return launch_energy_lds_image(ctx, pl, a, s);
-  return launch_energy_slotted(ctx, pl, a, s);
+  return launch_energy_slotted(ctx, pl, a, s);  // LDS-image: the pixel-major step's energy
 }
 
 // ---------------------------------------------------------------------------

@@ -1,15 +1,21 @@
 // rhmc_perwave.hpp — the one-wave-per-chain kernels of the RHMC leapfrog
-// engine: the generic LDS-image kernels (K <= 16) and the slotted *_win_kernel
-// templates that run a gradient policy (WinG / WinEG / WinGG of
-// rhmc_windowed.hpp, DenseG of rhmc_dense.hpp).  Device code only: the host
-// side that selects and launches them is rhmc_select.hpp / rhmc_launch.hpp.
+// engine: the slotted *_win_kernel templates, which run a gradient policy (LdsG
+// below, WinG / WinEG / WinGG of rhmc_windowed.hpp, DenseG of rhmc_dense.hpp),
+// and the LDS-image step leapfrog_kernel<MAXK>.  The energy's T, support test,
+// prior and pair potential and the gradient's frame are written once in the
+// slotted kernels; a policy is where the image and the tables live, and the
+// pixel loop.  The LDS-image step (K <= 16) keeps its own kernel: run through
+// the slotted frame it lost 8 % at MAXK = 16.  Device
+// code only: the host side that selects and launches them is rhmc_select.hpp /
+// rhmc_launch.hpp.
 //
-// Work decomposition: one wave64 per chain; a workgroup of W waves shares the
-// data image D, staged once into LDS with coalesced loads.  After that single
-// workgroup barrier every wave runs its chain independently (only wave-local
-// LDS hand-offs), n_steps steps fused in one launch with (q, p) in registers.
+// Work decomposition: one wave64 per chain, n_steps steps fused in one launch
+// with (q, p) in registers.  LDS-image (LdsG, leapfrog_kernel): a workgroup of
+// W waves shares the data image D, staged once into LDS with coalesced loads;
+// after that single workgroup barrier every wave runs its chain independently
+// (only wave-local LDS hand-offs).
 //
-// Per gradient evaluation (the inner loop, sampler_RHMC.py:365-425):
+// Per LDS-image gradient evaluation (the inner loop, sampler_RHMC.py:365-425):
 //   * the Gaussian PSF is separable: PSF[i][j] = ex[i]*ey[j] with
 //     ex[i] = exp(-((i+.5)-x)^2/(2s^2)), ey[j] = exp(-((j+.5)-y)^2/(2s^2))/(2 pi s^2)
 //     -> (R + C) exps per star instead of R*C (utils.py:475-486);
@@ -32,12 +38,6 @@
 #include "rhmc_windowed.hpp"
 
 namespace rhmc {
-
-struct Geometry {
-  int rows, cols, npix, npl;  // npl = ceil(npix / 64) pixels per lane
-  int di, dj;                 // pixel index step of 64 as (rows, cols)
-  double* work;               // WinGG's per-chain factor tables (from 65 stars), else null
-};
 
 struct Tables {  // per-wave LDS tables, K stars
   double* ex;  // [K][rows]
@@ -175,7 +175,7 @@ struct LeapArgs {
   int K, n_steps;
   Geometry g;
   Consts c;
-  // ragged sets (rhmc_leapfrog_ragged_device, the slotted kernels only): chain
+  // ragged sets (rhmc_leapfrog_ragged_device): chain
   // i is row rows[i] (NULL: row i) of [*][ld] arrays with Kc[row] stars; K is
   // then the largest star count of the launch (it sizes LDS).  Kc NULL: every
   // chain has K stars in rows of 3K.
@@ -200,6 +200,73 @@ __device__ __forceinline__ int64_t stage_image(double* sD, const double* __restr
   __syncthreads();
   return (int64_t)blockIdx.x * waves_per_wg + (threadIdx.x / kWave);
 }
+
+// Gradient policy of the slotted kernels on the image in LDS (the plan's
+// Family::LdsImage, K <= MAXK <= 16, any PSF width): D staged once per
+// workgroup, behind it one region of separable tables per wave, sized by the
+// launch's K and laid out by the chain's (ragged sets).  One slot; `lc` unused.
+template <int MAXK>
+struct LdsG {
+  static __host__ __device__ constexpr size_t lds_bytes(int waves, int K, int rows, int cols) {
+    return ((size_t)rows * cols + waves * table_doubles(K, rows, cols)) * sizeof(double);
+  }
+  struct Ctx {
+    const double* sD;  // LDS [npix]
+    double* tab;       // this wave's table region
+    Geometry g;
+  };
+  static __device__ __forceinline__ Ctx setup(double* lds, const double* D, int K,
+                                              const Geometry& g) {
+    stage_image(lds, D, g.npix, blockDim.x / kWave);
+    return Ctx{lds, lds + g.npix + (threadIdx.x / kWave) * table_doubles(K, g.rows, g.cols), g};
+  }
+  template <int SLOTS>
+  static __device__ __forceinline__ void gradient(const Ctx& g, int K, const double (&f)[SLOTS],
+                                                  const double (&x)[SLOTS],
+                                                  const double (&y)[SLOTS], const Consts& c,
+                                                  const LeanConsts&, bool with_metric,
+                                                  double (&gf)[SLOTS], double (&gx)[SLOTS],
+                                                  double (&gy)[SLOTS]) {
+    static_assert(SLOTS == 1, "lane k < K <= 16 owns star k");
+    rhmc::gradient<MAXK>(g.sD, carve_tables(g.tab, K, g.g), K, f[0], x[0], y[0], g.g, c,
+                         with_metric, gf[0], gx[0], gy[0]);
+  }
+  // sum over pixels of Lambda - D log Lambda (sampler_RHMC.py:319-327)
+  template <int SLOTS>
+  static __device__ __forceinline__ double potential(const Ctx& g, int K,
+                                                     const double (&f)[SLOTS],
+                                                     const double (&x)[SLOTS],
+                                                     const double (&y)[SLOTS], const Consts& c,
+                                                     const LeanConsts&) {
+    static_assert(SLOTS == 1, "lane k < K <= 16 owns star k");
+    const Geometry& geo = g.g;
+    const Tables tab = carve_tables(g.tab, K, geo);
+    const int lane = lane_id();
+    build_tables(tab, K, x[0], y[0], geo, c);
+    double fk[MAXK];
+#pragma unroll
+    for (int k = 0; k < MAXK; ++k) fk[k] = (k < K) ? bcast(f[0], k) : 0.0;
+    double v = 0.0;
+    int i = lane / geo.cols, j = lane - (lane / geo.cols) * geo.cols;
+    for (int tt = 0; tt < geo.npl; ++tt) {
+      const int pix = lane + kWave * tt;
+      if (pix < geo.npix) {
+        double lam = c.B;
+#pragma unroll
+        for (int k = 0; k < MAXK; ++k)
+          if (k < K) lam = fma(fk[k], tab.ex[k * geo.rows + i] * tab.ey[k * geo.cols + j], lam);
+        v += lam - g.sD[pix] * log(lam);
+      }
+      j += geo.dj;
+      i += geo.di;
+      if (j >= geo.cols) {
+        j -= geo.cols;
+        ++i;
+      }
+    }
+    return wave_sum(v);
+  }
+};
 
 // Chain state of one wave: lane k < K owns star k (UNIFORM: K == 1 and every
 // lane mirrors star 0, so no cross-lane reduction is needed).
@@ -354,8 +421,9 @@ __global__ void __launch_bounds__(256) leapfrog_kernel(LeapArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// Windowed kernels (rhmc_windowed.hpp): any square image, 1 <= K <= 256, one
-// wave per chain, star 64 s + lane in register slot s (SLOTS = 1, 2, 4).
+// The slotted frame: one wave per chain, star 64 s + lane in register slot s
+// (SLOTS = 1 for LdsG's energy and gradient; 1, 2, 4 for the windowed and dense
+// policies up to 256 stars; WinGG to 16).
 template <int SLOTS>
 struct WinState {
   double f[SLOTS], x[SLOTS], y[SLOTS], pf[SLOTS], px[SLOTS], py[SLOTS];
@@ -529,7 +597,7 @@ __device__ __forceinline__ void run_steps_win(WinState<SLOTS>& s, int n_steps, i
 template <class G, int SLOTS>
 __global__ void __launch_bounds__(256) leapfrog_win_kernel(LeapArgs a) {
   extern __shared__ double lds[];
-  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g.rows, a.g.cols, a.g.work);
+  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g);
   const Consts& c = a.c;
   const int W = blockDim.x / kWave;
   const int64_t chain = (int64_t)blockIdx.x * W + (threadIdx.x / kWave);
@@ -562,27 +630,6 @@ struct GradArgs {
   Consts c;
 };
 
-template <int MAXK>
-__global__ void __launch_bounds__(256) gradient_kernel(GradArgs a) {
-  extern __shared__ double lds[];
-  const int W = blockDim.x / kWave;
-  const int64_t chain = stage_image(lds, a.D, a.g.npix, W);
-  if (chain >= a.n_chains) return;
-  const int lane = lane_id();
-  const int K = a.K;
-  const Tables tab = carve_tables(lds + a.g.npix + (threadIdx.x / kWave) * table_doubles(K, a.g.rows, a.g.cols), K, a.g);
-  const bool owner = lane < K;
-  const int64_t base = chain * 3 * (int64_t)K + 3 * (owner ? lane : 0);
-  const double f = a.q[base], x = a.q[base + 1], y = a.q[base + 2];
-  double gf, gx, gy;
-  gradient<MAXK>(lds, tab, K, f, x, y, a.g, a.c, a.with_metric != 0, gf, gx, gy);
-  if (owner) {
-    a.grad[base] = gf;
-    a.grad[base + 1] = gx;
-    a.grad[base + 2] = gy;
-  }
-}
-
 struct EnergyArgs {
   const double* q;
   const double* p;
@@ -593,99 +640,11 @@ struct EnergyArgs {
   int K, f_pos;
   Geometry g;
   Consts c;
-  // ragged sets (rhmc_energy_ragged_device, slotted kernels only), as LeapArgs
+  // ragged sets (rhmc_energy_ragged_device), as LeapArgs
   const int32_t* Kc = nullptr;
   const int64_t* rows = nullptr;
   int64_t ld = 0;
 };
-
-// V (sampler_RHMC.py:294-351) and T at H(q) (:353-363), one wave per chain.
-// Ragged sets (a.Kc): the chain's row and star count; the wave's table region
-// is sized by the set's largest K (a.K), laid out by the chain's.
-template <int MAXK>
-__global__ void __launch_bounds__(256) energy_kernel(EnergyArgs a) {
-  extern __shared__ double lds[];
-  const Geometry& g = a.g;
-  const Consts& c = a.c;
-  const int W = blockDim.x / kWave;
-  const int64_t chain = stage_image(lds, a.D, g.npix, W);
-  if (chain >= a.n_chains) return;
-  const int lane = lane_id();
-  int64_t row, ld;
-  int K;
-  chain_row(a, chain, row, K, ld);
-  const Tables tab = carve_tables(
-      lds + g.npix + (threadIdx.x / kWave) * table_doubles(a.K, g.rows, g.cols), K, g);
-  const bool owner = lane < K;
-  const int64_t base = row * ld + 3 * (owner ? lane : 0);
-  const double f = a.q[base], x = a.q[base + 1], y = a.q[base + 2];
-
-  if (a.T) {
-    double t1 = 0.0, t2 = 0.0;
-    if (owner) {
-      const double pf = a.p[base], px = a.p[base + 1], py = a.p[base + 2];
-      const double hff = H_ff(f, c), hxx = H_xx(f, c);
-      t1 = pf * pf / hff + px * px / hxx + py * py / hxx;
-      t2 = log(fabs(hff)) + log(fabs(hxx)) + log(fabs(hxx));
-    }
-    t1 = wave_sum(t1);
-    t2 = wave_sum(t2);
-    if (lane == 0) a.T[chain] = (t1 + t2) / 2.0;
-  }
-  if (!a.V) return;
-
-  // Infinite potential outside the support (:303-317)
-  bool bad = false;
-  if (owner) {
-    if ((a.f_pos & RHMC_V_FLUX_WALL) && f < c.f_lim) bad = true;
-    if (!(a.f_pos & RHMC_V_NO_POSCHECK) &&
-        (x < -1.0 || x > (double)(g.rows + 1) || y < -1.0 || y > (double)(g.cols + 1)))
-      bad = true;
-  }
-  if (__any(bad)) {
-    if (lane == 0) a.V[chain] = INFINITY;
-    return;
-  }
-
-  build_tables(tab, K, x, y, g, c);
-  double fk[MAXK];
-#pragma unroll
-  for (int k = 0; k < MAXK; ++k) fk[k] = (k < K) ? bcast(f, k) : 0.0;
-  double v = 0.0;
-  int i = lane / g.cols, j = lane - (lane / g.cols) * g.cols;
-  for (int tt = 0; tt < g.npl; ++tt) {
-    const int pix = lane + kWave * tt;
-    if (pix < g.npix) {
-      double lam = c.B;
-#pragma unroll
-      for (int k = 0; k < MAXK; ++k)
-        if (k < K) lam = fma(fk[k], tab.ex[k * g.rows + i] * tab.ey[k * g.cols + j], lam);
-      v += lam - lds[pix] * log(lam);
-    }
-    j += g.dj;
-    i += g.di;
-    if (j >= g.cols) {
-      j -= g.cols;
-      ++i;
-    }
-  }
-  v = wave_sum(v);
-  if (c.use_prior) {  // V_prior accumulated per star, added after the sum (:326, :329-330)
-    const double vp = wave_sum(owner ? c.alpha * log(f) + c.vprior : 0.0);
-    v += vp;
-  }
-  if (c.use_Vc) {  // 0.5 beta sum_{a,b} R_ab^-pow with R_aa -> 1e32 (:332-349)
-    double s = 0.0;
-    for (int jj = 0; jj < K; ++jj) {
-      const double X = bcast(x, jj), Y = bcast(y, jj);
-      double R = sqrt((X - x) * (X - x) + (Y - y) * (Y - y));
-      if (fabs(R) < 1e-10) R = 1e32;
-      s += pow(1.0 / R, c.vc_pow);
-    }
-    v += 0.5 * c.beta * wave_sum(owner ? s : 0.0);
-  }
-  if (lane == 0) a.V[chain] = v;
-}
 
 // ---------------------------------------------------------------------------
 // Alternative integrators, windowed gradient, lanes = stars:
@@ -705,7 +664,7 @@ __device__ __forceinline__ double dVdq_rhmc_f(double f, double pf, const Consts&
 template <class G, int SOLVER, int SLOTS>
 __global__ void __launch_bounds__(256) integrate_win_kernel(LeapArgs a, int f_pos) {
   extern __shared__ double lds[];
-  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g.rows, a.g.cols, a.g.work);
+  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g);
   const Consts& c = a.c;
   const int W = blockDim.x / kWave;
   const int64_t chain = (int64_t)blockIdx.x * W + (threadIdx.x / kWave);
@@ -800,7 +759,7 @@ __device__ __forceinline__ void hmc_random_win_body(double* lds, const LeapArgs&
                                                     const double* __restrict__ dtv,
                                                     const int32_t* __restrict__ steps,
                                                     const DiagArgs& dg) {
-  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g.rows, a.g.cols, a.g.work);
+  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g);
   const Consts& c = a.c;
   const int W = blockDim.x / kWave;
   const int64_t chain = (int64_t)blockIdx.x * W + (threadIdx.x / kWave);
@@ -894,11 +853,11 @@ __device__ __forceinline__ void win_load_q(const double* q, int64_t row, int64_t
   }
 }
 
-// Large-image gradient (windowed), one wave per chain.
+// dVdq or dphidq of policy G, one wave per chain.
 template <class G, int SLOTS>
 __global__ void __launch_bounds__(256) gradient_win_kernel(GradArgs a) {
   extern __shared__ double lds[];
-  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g.rows, a.g.cols, a.g.work);
+  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g);
   const int W = blockDim.x / kWave;
   const int64_t chain = (int64_t)blockIdx.x * W + (threadIdx.x / kWave);
   if (chain >= a.n_chains) return;
@@ -918,11 +877,13 @@ __global__ void __launch_bounds__(256) gradient_win_kernel(GradArgs a) {
   }
 }
 
-// Large-image V and T (windowed tables, pixel-major V).
+// V (sampler_RHMC.py:294-351) and T at H(q) (:353-363), one wave per chain:
+// the policy's potential, the rest here.  Ragged sets (a.Kc): the chain's row
+// and star count; the policy's setup sees the set's largest K (a.K).
 template <class G, int SLOTS>
 __global__ void __launch_bounds__(256) energy_win_kernel(EnergyArgs a) {
   extern __shared__ double lds[];
-  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g.rows, a.g.cols, a.g.work);
+  const typename G::Ctx gctx = G::setup(lds, a.D, a.K, a.g);
   const Geometry& g = a.g;
   const Consts& c = a.c;
   const int W = blockDim.x / kWave;

@@ -34,6 +34,14 @@ struct Consts {
   int counter_max, use_prior, use_Vc, pad;
 };
 
+// The image as the one-wave-per-chain kernels walk it (LeapArgs, GradArgs,
+// EnergyArgs, HessArgs; a gradient policy's setup).
+struct Geometry {
+  int rows, cols, npix, npl;  // npl = ceil(npix / 64) pixels per lane
+  int di, dj;                 // pixel index step of 64 as (rows, cols)
+  double* work;               // WinGG's per-chain factor tables (from 65 stars), else null
+};
+
 // What samplers.lightsource_gym.RHMC_random_diag's trajectory (samplers.py:
 // 766-800) adds to an HMC_random launch: the one global step, 1/factor1 of the
 // mass matrix M = diag(1/f, f factor1, f factor1) per star (:574-600), and the

@@ -426,8 +426,8 @@ struct WinG {
     const double* D;
     int rows, cols;
   };
-  static __device__ __forceinline__ Ctx setup(double* lds, const double* D, int K, int rows,
-                                              int cols, double* /*work*/) {
+  static __device__ __forceinline__ Ctx setup(double* lds, const double* D, int K,
+                                              const Geometry& geo) {
     exp_tab_fill(lds);
     __syncthreads();
     double* base = lds + kExpTab + (threadIdx.x / kWave) * win_table_doubles(K);
@@ -435,8 +435,8 @@ struct WinG {
     g.etab = lds;
     g.tab = WinTables{base, base + K * kTabW};
     g.D = D;
-    g.rows = rows;
-    g.cols = cols;
+    g.rows = geo.rows;
+    g.cols = geo.cols;
     return g;
   }
   template <int SLOTS>
@@ -471,16 +471,16 @@ struct WinEG {
     const double* D;
     int rows, cols;
   };
-  static __device__ __forceinline__ Ctx setup(double* lds, const double* D, int K, int rows,
-                                              int cols, double* /*work*/) {
+  static __device__ __forceinline__ Ctx setup(double* lds, const double* D, int K,
+                                              const Geometry& geo) {
     exp_tab_fill(lds);
     __syncthreads();
     Ctx g;
     g.etab = lds;
     g.ey = lds + kExpTab + (threadIdx.x / kWave) * (size_t)K * kTabW;
     g.D = D;
-    g.rows = rows;
-    g.cols = cols;
+    g.rows = geo.rows;
+    g.cols = geo.cols;
     return g;
   }
   template <int SLOTS>
@@ -503,18 +503,18 @@ struct WinGG {
   static __host__ __device__ size_t lds_bytes(int, int) { return kExpTab * sizeof(double); }
   static __host__ __device__ size_t work_doubles(int K) { return win_table_doubles(K); }
   using Ctx = WinG::Ctx;
-  static __device__ __forceinline__ Ctx setup(double* lds, const double* D, int K, int rows,
-                                              int cols, double* work) {
+  static __device__ __forceinline__ Ctx setup(double* lds, const double* D, int K,
+                                              const Geometry& geo) {
     exp_tab_fill(lds);
     __syncthreads();
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-    double* base = work + wave * (int64_t)work_doubles(K);
+    double* base = geo.work + wave * (int64_t)work_doubles(K);
     Ctx g;
     g.etab = lds;
     g.tab = WinTables{base, base + K * kTabW};
     g.D = D;
-    g.rows = rows;
-    g.cols = cols;
+    g.rows = geo.rows;
+    g.cols = geo.cols;
     return g;
   }
   template <int SLOTS>

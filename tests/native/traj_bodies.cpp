@@ -40,7 +40,7 @@
 // energy's body (one star with it leaves the register window), so use_Vc is
 // an input; rhmc_mh takes RHMC_OPT_MH_FUSED in its place:
 //   regwin1/IMG/DT                energy_k1_tiledr<IMG, DT>
-//   ldsimage/MAXK                 energy_kernel<MAXK>, gradient_kernel<MAXK>
+//   ldsimage/MAXK                 energy_ / gradient_win_kernel<LdsG<MAXK>, 1>
 //   slotted/WinEG/1               energy_win_kernel<WinEG, 1>
 //   slotted/WinG/1                gradient_win_kernel<WinG, 1>
 //   slotted/WinGG/SLOTS           energy_ / gradient_win_kernel<WinGG, SLOTS>
@@ -75,6 +75,7 @@ template <int N> static std::string str(IntTag<N>) { return std::to_string(N); }
 template <int IMG> static std::string str(TypeTag<DenseG<IMG>>) {
   return "Dense" + std::to_string(IMG);
 }
+template <int MAXK> static std::string str(TypeTag<LdsG<MAXK>>) { return std::to_string(MAXK); }
 
 // The body that the launcher of `op` runs for a plan of a kernel family on an
 // image of `side` px.  A tag IMG other than the side is no kernel of that image.
@@ -107,13 +108,18 @@ static std::string family_key(Op op, const Plan& pl, int side) {
       };
       return step ? with_multiwin<true>(pl, name) : with_multiwin<false>(pl, name);
     }
-    case Family::LdsImage:  // launch_lds_image
-      return with_maxk(pl, [](auto maxk) { return "ldsimage/" + str(maxk); });
+    case Family::LdsImage: {  // launch_leapfrog; launch_energy_slotted, launch_gradient
+      auto name = [](auto g, auto) { return "ldsimage/" + str(g); };
+      if (op == Op::Step) return with_maxk(pl, [](auto maxk) { return "ldsimage/" + str(maxk); });
+      if (op == Op::Energy) return with_perwave_energy_policy(pl, name);
+      if (op == Op::Gradient) return with_perwave_policy(pl, name);
+      return std::string("ldsimage/no-such-kernel");  // no other operation has one
+    }
     default: break;
   }
   auto name = [](auto g, auto slots) { return "slotted/" + str(g) + "/" + str(slots); };
-  return op == Op::Energy ? with_energy_policy(pl, name)  // launch_energy_slotted
-                          : with_policy(pl, name);
+  if (op == Op::Energy) return with_perwave_energy_policy(pl, name);  // launch_energy_slotted
+  return op == Op::Gradient ? with_perwave_policy(pl, name) : with_policy(pl, name);
 }
 
 static double inv_two_sig2_of(double fwhm) {

@@ -4,8 +4,8 @@ tests/native/traj_bodies.cpp in its `energy`, `gradient` and `mh` modes (a
 host compiler, csrc/rhmc_select.hpp and csrc/rhmc_dispatch.hpp alone) names the
 body that each operation launches for a shape, by calling the switches of
 rhmc_dispatch.hpp that csrc/rhmc_launch.hpp's launchers call
-(launch_energy, launch_energy_slotted, launch_energy_lds_image;
-launch_gradient; run_mh, launch_mh_k1, launch_mh_pk).  The pair potential
+(launch_energy, launch_energy_slotted; launch_gradient; run_mh, launch_mh_k1,
+launch_mh_pk).  The pair potential
 changes the energy's body, so the program takes use_Vc per case; rhmc_mh takes
 RHMC_OPT_MH_FUSED in its place.  BODIES is written from the instantiations
 those switches can reach, not from the program:
@@ -30,7 +30,7 @@ from test_traj_bodies import traj_bodies  # noqa: F401 (the fixture)
 
 _DT = ("float", "double")
 _PER_WAVE = (
-    # energy_kernel<MAXK>, gradient_kernel<MAXK>
+    # energy_ / gradient_win_kernel<LdsG<MAXK>, 1>
     ["ldsimage/%d" % k for k in (1, 2, 4, 8, 16)]
     # energy_ / gradient_win_kernel<WinGG, SLOTS>, <DenseG<IMG>, SLOTS>
     + ["slotted/WinGG/%d" % s for s in (2, 4, 8, 16)]

@@ -1,7 +1,7 @@
 """Every kernel body of rhmc_energy, rhmc_gradient and rhmc_mh.
 
 rhmc_energy launches one of 22 kernel bodies (csrc/rhmc_launch.hpp:
-launch_energy, launch_energy_slotted, launch_energy_lds_image), rhmc_gradient
+launch_energy, launch_energy_slotted), rhmc_gradient
 one of 16 (launch_gradient), each computing dVdq (kind 0) or dphidq (kind 1),
 and rhmc_mh one of 8 fused bodies (launch_mh_k1, launch_mh_pk) or the
 four-kernel loop in its two forms (run_mh: one thread per chain below 8 stars,

@@ -4,8 +4,9 @@ tests/native/traj_bodies.cpp in its `step` mode (a host compiler,
 csrc/rhmc_select.hpp and csrc/rhmc_dispatch.hpp alone) names the body that
 rhmc_leapfrog launches for a shape, by calling the switches of
 rhmc_dispatch.hpp that csrc/rhmc_launch.hpp's launchers call (launch_leapfrog:
-launch_tiledr, launch_tiledl, launch_multi, launch_kr, launch_leap_slotted,
-launch_lds_image).  Unlike the other two operations the step's body depends on
+launch_tiledr, launch_tiledl, launch_multi, launch_kr, launch_leap_slotted;
+the LDS-image step in launch_leapfrog itself).  Unlike the other two
+operations the step's body depends on
 the chain count, on RHMC_OPT_WINDOW_SPLIT and on the PSF width, so the program
 takes those per case.  BODIES is written from the instantiations those
 switches can reach, not from the program:

@@ -3,8 +3,16 @@
 (tools only; compare two builds bit for bit with tools/lib_cmp.py).
 
 --op leapfrog (default): a workload's full leapfrog launch; q, p, iteration
-counts and status.
+counts and status.  KxSIDE names the workload S<SIDE>K<K> (5 chains unless
+--chains says otherwise), on which --no-prior, --vc (the pair potential),
+--fwhm, --steps and --inexact (an image that fp32 does not hold) apply.
   RHMC_LIB=build/variants/lib_x.so python tools/lib_dump.py C2 out.npz [--chains N]
+  python tools/lib_dump.py 3x40 out.npz --kernel generic --vc
+--op energy: V and T of the same starts (--no-T: V alone), --f-pos the bits of
+rhmc_energy (1: flux wall, 2: no position check).  --op gradient: dVdq and
+dphidq (grad0, grad1).  Both follow --kernel like the step: `auto` sends one
+star on an fp32-exact 32/48/64-px image to the register-window energy, so a
+comparison of the LDS-image bodies (ldsimage/MAXK) passes --kernel generic.
 --op hmc_random / diag_random: the trajectories of a KxSIDE field built as
 tools/diag_bench.py builds it, with unequal lengths of at most 40 steps; q, p,
 status and, for diag_random with --trace, the trace.  --wall puts a flux wall
@@ -12,6 +20,7 @@ just under every chain's faintest star and sends that star towards it.
   python tools/lib_dump.py 3x48 out.npz --op diag_random --kernel multiwin --chains 5"""
 import argparse
 import os
+import re
 import sys
 
 import numpy as np
@@ -24,16 +33,41 @@ from rhmc_amd import capi, workloads  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("workload", help="a workload name (leapfrog) or KxSIDE (trajectories)")
 ap.add_argument("out")
-ap.add_argument("--op", choices=["leapfrog", "hmc_random", "diag_random"], default="leapfrog")
+ap.add_argument("--op", default="leapfrog",
+                choices=["leapfrog", "energy", "gradient", "hmc_random", "diag_random"])
 ap.add_argument("--kernel", default="auto", help="kernel family (capi.KERNELS)")
 ap.add_argument("--chains", type=int, default=None)
 ap.add_argument("--dt", type=float, default=None, help="trajectories: the step (diag_bench's)")
 ap.add_argument("--trace", action="store_true", help="diag_random: save the trace too")
 ap.add_argument("--wall", action="store_true", help="trajectories: a flux wall that chains cross")
+ap.add_argument("--no-prior", action="store_true", help="KxSIDE: the flux prior off")
+ap.add_argument("--vc", action="store_true", help="KxSIDE: the pair potential on")
+ap.add_argument("--fwhm", type=float, default=None, help="KxSIDE: the PSF's FWHM in px")
+ap.add_argument("--steps", type=int, default=None, help="leapfrog: steps of the launch")
+ap.add_argument("--inexact", action="store_true", help="KxSIDE: D + 0.1, not exact in fp32")
+ap.add_argument("--f-pos", type=int, default=0, help="energy: rhmc_energy's f_pos bits")
+ap.add_argument("--no-T", action="store_true", help="energy: V alone (no momenta)")
+
+
+def workload(args):
+    """The named workload, or S<SIDE>K<K> for KxSIDE with the options applied."""
+    m = re.fullmatch(r"(\d+)x(\d+)", args.workload)
+    if not m:
+        return workloads.make(args.workload, n_chains=args.chains)
+    K, side = int(m.group(1)), int(m.group(2))
+    wl = workloads.make("S%dK%d" % (side, K), n_chains=args.chains or 5)
+    wl.params.update(use_prior=not args.no_prior, use_Vc=args.vc)
+    if args.fwhm:
+        wl.params["fwhm_pix"] = args.fwhm
+    if args.inexact:
+        wl.D = wl.D + 0.1
+    return wl
 
 
 def leapfrog(args):
-    wl = workloads.make(args.workload, n_chains=args.chains)
+    wl = workload(args)
+    if args.steps is not None:
+        wl.n_steps = args.steps
     P = capi.make_params(**wl.params)
     dev = torch.device("cuda:0")
     ctx = capi.Context(wl.D, device=0)
@@ -48,6 +82,30 @@ def leapfrog(args):
     np.savez(args.out, q=q.cpu().numpy(), p=p.cpu().numpy(), it=it.cpu().numpy(),
              st=st.cpu().numpy())
     print("%s: %d chains x %d steps -> %s" % (args.workload, wl.n_chains, wl.n_steps, args.out))
+
+
+def energy(args):
+    wl = workload(args)
+    ctx = capi.Context(wl.D, device=0, kernel=args.kernel)
+    dev = torch.device("cuda:0")
+    q, p = torch.from_numpy(wl.q0).to(dev), torch.from_numpy(wl.p0).to(dev)
+    V = torch.zeros(wl.n_chains, dtype=torch.float64, device=dev)
+    T = torch.zeros_like(V)
+    ctx.energy_device(capi.make_params(**wl.params), q.data_ptr(),
+                      0 if args.no_T else p.data_ptr(), V.data_ptr(),
+                      0 if args.no_T else T.data_ptr(), wl.n_chains, wl.K, f_pos=args.f_pos)
+    torch.cuda.synchronize()
+    np.savez(args.out, V=V.cpu().numpy(), T=T.cpu().numpy())
+    print("energy %s %s f_pos %d: %d chains, %d infinite -> %s" % (
+        args.workload, args.kernel, args.f_pos, wl.n_chains, int(torch.isinf(V).sum()), args.out))
+
+
+def gradient(args):
+    wl = workload(args)
+    ctx = capi.Context(wl.D, device=0, kernel=args.kernel)
+    P = capi.make_params(**wl.params)
+    np.savez(args.out, grad0=ctx.gradient(P, wl.q0, 0), grad1=ctx.gradient(P, wl.q0, 1))
+    print("gradient %s %s: %d chains -> %s" % (args.workload, args.kernel, wl.n_chains, args.out))
 
 
 def trajectories(args):
@@ -87,7 +145,7 @@ def trajectories(args):
 
 def main(argv=None):
     args = ap.parse_args(argv)
-    (leapfrog if args.op == "leapfrog" else trajectories)(args)
+    {"leapfrog": leapfrog, "energy": energy, "gradient": gradient}.get(args.op, trajectories)(args)
 
 
 if __name__ == "__main__":

@@ -301,7 +301,11 @@ int rhmc_leapfrog_device(rhmc_ctx* ctx, const rhmc_params* P, double* d_q,
  * K_min and K_max must need the same register slots (1-64, 65-128, 129-256,
  * 257-512, 513-1024 stars), else RHMC_ERR_ARG, and a K the slotted kernels do not serve gives
  * RHMC_ERR_UNSUPPORTED.  Each chain's results equal those of a fixed-K call
- * on it (the kernels are batch-invariant).  Asynchronous on `stream`.
+ * on it (the kernels are batch-invariant).  Entries of a row past 3 d_K[row],
+ * rows not in d_rows, and d_K of such rows are neither read nor written
+ * (tests/test_gpu_ragged_bodies.py pins this for every kernel body of the
+ * step, tests/test_gpu_energy_bodies.py for the energy).  Asynchronous on
+ * `stream`.
  */
 int rhmc_ragged_ok(rhmc_ctx* ctx, const rhmc_params* P, int32_t K, int32_t* ok);
 /* n_steps RHMC_single_step()s on the set; q, p rows updated in place. */

@@ -54,6 +54,17 @@
 //   traj_bodies energy|gradient side K img_f32 kernel n_chains use_Vc fwhm [...]   one per seven
 //   traj_bodies mh sweep
 //   traj_bodies mh side K img_f32 kernel n_chains mh_fused fwhm [...]
+//
+// `ragged`: a ragged chain set (rhmc_leapfrog_ragged_device, launch_leapfrog_ragged;
+// rhmc_energy_ragged_device, launch_energy_ragged).  K is the launch's K_max,
+// whose plans the two launchers take; `none` where ragged_family() is 0, else
+// the step's body and the energy's, STEP|ENERGY:
+//   pixmajor/IMG/ragged           leapfrog_pk<IMG, 10, IMPLICIT, true>
+//   slotted/POLICY/SLOTS          leapfrog_win_kernel<G, SLOTS>
+//   ldsimage/MAXK | slotted/...   energy_win_kernel<G, SLOTS>
+// Built and run by tests/test_ragged_bodies.py.
+//   traj_bodies ragged sweep                                          the distinct pairs
+//   traj_bodies ragged side K img_f32 kernel n_chains use_Vc fwhm [...]   one pair per seven
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -141,6 +152,24 @@ static std::string mh_key(const SelectIn& s, int K, int64_t n, double its) {
   });
 }
 
+// launch_leapfrog_ragged: with_side2 for a pixel-major plan (the RAGGED
+// instantiation), else launch_leap_slotted's with_policy; launch_energy_ragged:
+// launch_energy_slotted's with_perwave_energy_policy.
+static std::string ragged_key(const SelectIn& s, bool use_Vc, double its, int K, int64_t n) {
+  if (!ragged_family(s, use_Vc, its, K)) return "none";
+  const Plan st = select(s, use_Vc, its, Op::Step, K, n);
+  const Plan en = select(s, use_Vc, its, Op::Energy, K, n);
+  if (st.family == Family::Unsupported || en.family == Family::Unsupported) return "Unsupported";
+  const std::string step =
+      st.family == Family::PixMajor ? family_key(Op::Step, st, s.rows) + "/ragged"
+      : st.family == Family::Slotted ? family_key(Op::Step, st, s.rows)
+                                     : std::string("no-ragged-step");
+  const std::string energy = en.family == Family::Slotted || en.family == Family::LdsImage
+                                 ? family_key(Op::Energy, en, s.rows)
+                                 : std::string("no-ragged-energy");
+  return step + "|" + energy;
+}
+
 // A mode of the command line: its operation, the sweep's values and what the
 // sixth argument of a point sets (none: five arguments, the reference PSF).
 enum class Flag { None, WindowSplit, UseVc, MhFused };
@@ -152,6 +181,7 @@ struct Mode {
   std::vector<int64_t> chains;
   std::vector<int> flags;
   std::vector<double> fwhms;
+  bool ragged = false;   // a ragged set: ragged_key() of the step's and the energy's plans
 };
 // The reference PSF, FWHM 3.5 px, and 3.8 px, inside (3.555, 4.06]:
 // reg_window_ok(32) holds, reg_window_ok(28) does not, and the 32-px windows of
@@ -166,6 +196,9 @@ static const Mode kModes[] = {
     {"energy", Op::Energy, Flag::UseVc, kOpSides, {4, 65536}, {0, 1}, kBothFwhm},
     {"gradient", Op::Gradient, Flag::UseVc, kOpSides, {4, 65536}, {0, 1}, kBothFwhm},
     {"mh", Op::MhFused, Flag::MhFused, kOpSides, {4, 65536}, {0, 1}, kBothFwhm},
+    // 24 px: below the register kernels' 32, the windowed kernel by rule from 17 stars
+    {"ragged", Op::Step, Flag::UseVc, {24, 32, 40, 48, 64, 96, 256}, {4, 65536}, {0, 1}, kBothFwhm,
+     true},
     {nullptr, Op::HmcRandom, Flag::None, {32, 48, 64, 96}, {4, 65536}, {0}, kRefFwhm},
 };
 
@@ -182,6 +215,7 @@ static std::string point_key(const Mode& m, int side, int K, bool f32, int kerne
   if (m.flag == Flag::MhFused) s.mh_fused = flag;
   const double its = inv_two_sig2_of(fwhm);
   if (m.op == Op::MhFused) return mh_key(s, K, n, its);
+  if (m.ragged) return ragged_key(s, flag != 0, its, K, n);
   return family_key(m.op, select(s, m.flag == Flag::UseVc && flag, its, m.op, K, n), side);
 }
 
@@ -205,6 +239,7 @@ int main(int argc, char** argv) {
                 for (double fwhm : m->fwhms) {
                   const std::string k = point_key(*m, side, K, f32 != 0, kernel, n, flag, fwhm);
                   if (k == "Unsupported" && !window_exact(inv_two_sig2_of(fwhm))) continue;
+                  if (k == "none") continue;  // no ragged family: one packed call per K
                   keys.insert(k);
                 }
     for (const std::string& k : keys) std::puts(k.c_str());
@@ -212,7 +247,7 @@ int main(int argc, char** argv) {
   }
   const int per = flagged ? 7 : 5;
   if (argc < per + 1 || (argc - 1) % per != 0) {
-    std::fprintf(stderr, "usage: %s [integrate|step|energy|gradient|mh] sweep | side K img_f32 "
+    std::fprintf(stderr, "usage: %s [integrate|step|energy|gradient|mh|ragged] sweep | side K img_f32 "
                          "kernel n_chains [window_split|use_Vc|mh_fused fwhm] [...]\n", prog);
     return 2;
   }

@@ -31,7 +31,10 @@ at rtol 1e-12 and atol 1e-12, the bars of test_gpu_parity):
 * `ragged` (every body a ragged set can reach, rhmc_select.hpp's
   ragged_family: all but regwin1 and ldsimage/1): one energy_ragged_device
   call on star counts from the low end of the row's slot class to the row's K,
-  rows permuted, ld > 3 K_max, bit-identical to the fixed-K calls.
+  rows permuted, ld > 3 K_max, bit-identical to the fixed-K calls; again
+  with quiet NaNs past 3 K[row] and in the unused row, whose d_K is 0, then
+  K_max + 1: V bit-identical (tests/test_gpu_ragged_bodies.py does the same
+  to the step).
   test_gpu_ragged.test_ragged_equals_fixed_K (slotted/Dense32/1,
   slotted/WinGG/2, ldsimage/16) and test_gpu_hugek.
   test_hugek_ragged_equals_fixed_K (slotted/WinGG/8) do the same on their
@@ -658,6 +661,25 @@ def test_energy_ragged_equals_fixed_K(gpu_lib, name):
             js = [j for j in range(N_RAGGED) if Ks[j] == k]
             V, _ = ctx.energy(P, q[order[js], :3 * k], None, f_pos=True)
             assert np.array_equal(Vg[js], V), (k, Vg[js], V)
+        # hostile padding: quiet NaNs of a known payload past 3 K[row] and in
+        # the unused row, whose d_K is 0, then K_max + 1 (0 would fault or
+        # corrupt if read, K_max + 1 computes on the poison): V bit-identical
+        unused = sorted(set(range(N_RAGGED + 1)) - set(order))
+        for bad_K in (0, K + 1):
+            qh = np.full(q.shape, 0x7FF8DEAD0000BEEF, np.uint64).view(np.float64)
+            for j, r in enumerate(order):
+                qh[r, :3 * Ks[j]] = q[r, :3 * Ks[j]]
+            assert np.isnan(qh[unused]).all() and np.isnan(qh[order[0], 3 * Ks[0]:]).all()
+            Kh = K_of.copy()
+            Kh[unused] = bad_K
+            qhd = torch.from_numpy(qh).to(dev)
+            Khd = torch.from_numpy(Kh).to(dev)
+            Vh = torch.zeros(N_RAGGED, dtype=torch.float64, device=dev)
+            ctx.energy_ragged_device(P, qhd.data_ptr(), ld, rows.data_ptr(), Khd.data_ptr(),
+                                     N_RAGGED, min(Ks), max(Ks), capi.V_FLUX_WALL, Vh.data_ptr())
+            torch.cuda.synchronize()
+            assert np.array_equal(Vh.cpu().numpy(), Vg), (bad_K, Vh.cpu().numpy(), Vg)
+            assert np.array_equal(qhd.cpu().numpy().view(np.uint64), qh.view(np.uint64))
 
 
 def _check_gradient(ctx, capi, r):

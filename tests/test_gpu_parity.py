@@ -46,7 +46,10 @@ def kernel_path(request, monkeypatch):
     body; on traj_c5 (K = 64, 256 px) multiwin/float/2/notab/4 under eleven
     values and slotted/WinG/1 under generic and windowed.  That is 24 of the 64
     bodies: no fp64 cache but the forced one-star ones, no side of 64, 96 or
-    128 px, no window split but 4.  tests/test_gpu_step_bodies.py runs all 64.
+    128 px, no window split but 4.  tests/test_gpu_step_bodies.py runs all 64,
+    and tests/test_gpu_ragged_bodies.py the 13 a ragged set can launch
+    (rhmc_leapfrog_ragged_device; the pixel-major kernel's RAGGED instantiations
+    among them, which no fixed-K call reaches).
 
     Which bodies of rhmc_energy and rhmc_gradient test_gradient_and_energy
     reaches (the keys of tests/test_energy_bodies.py, from the program's

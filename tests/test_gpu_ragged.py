@@ -12,8 +12,13 @@ counts in one launch, as rows of padded device arrays.
 * rhmc_kinetic_rows_device draws p = z sqrt(H(q)) bit for bit as the host
   (sampler_RHMC.py:1021-1022, the reference's metric, :260-292) and gives
   T(p, H(q)) (:353-363) to the last ulp of NumPy's;
-* the argument checks (mixed register slots, a star count no slotted kernel
-  serves)."""
+* the argument checks (mixed register slots at every slot-class edge, K_max
+  past 1024, K_min > K_max, ld < 3 K_max, n = 0 with null arrays; a star count
+  no slotted kernel serves).
+
+These compare a ragged step with a fixed-K call on zero padding; tests/
+test_gpu_ragged_bodies.py has a set per kernel body of the ragged step (13)
+against the oracle, under hostile padding and unused rows."""
 import numpy as np
 import pytest
 
@@ -115,6 +120,31 @@ def test_ragged_ok_and_argument_checks(gpu_lib):
     with pytest.raises(capi.RhmcError):               # ld too small for K_max
         ctx.leapfrog_ragged_device(P, q.data_ptr(), q.data_ptr(), 30, 0, K.data_ptr(), 2, 11,
                                    20, 1)
+    # every boundary of ragged_check, step and energy, on buffers that would
+    # hold any of these sets
+    ldb = 3 * 1025 + 8
+    qb = torch.zeros((2, ldb), dtype=torch.float64, device=dev)
+    pb = torch.zeros_like(qb)
+    Vb = torch.zeros(2, dtype=torch.float64, device=dev)
+
+    def both(ld, K_min, K_max, n=2, q=qb.data_ptr(), p=pb.data_ptr()):
+        yield lambda: ctx.leapfrog_ragged_device(P, q, p, ld, 0, K.data_ptr(), n, K_min, K_max, 1)
+        yield lambda: ctx.energy_ragged_device(P, q, ld, 0, K.data_ptr(), n, K_min, K_max,
+                                               capi.V_FLUX_WALL, Vb.data_ptr())
+
+    bad = [(ldb, lo, lo + 1) for lo in (64, 128, 256, 512)]     # two slot classes
+    bad += [(ldb, 1000, 1025), (ldb, 1025, 1025)]               # past the last kernel's 1024
+    bad += [(ldb, 13, 12), (ldb, 0, 12)]                        # K_min > K_max, K_min < 1
+    bad += [(3 * 20 - 1, 11, 20), (3 * 300 - 1, 257, 300)]      # ld = 3 K_max - 1
+    for args in bad:
+        for call in both(*args):
+            with pytest.raises(capi.RhmcError) as e:
+                call()
+            assert e.value.code == capi.RHMC_ERR_ARG, args
+    for call in both(3 * 20, 11, 20, n=0, q=0, p=0):            # n = 0: nothing is touched
+        call()
+    torch.cuda.synchronize()
+    assert not qb.any() and not pb.any() and not Vb.any()
     ctx.close()
     big = load_golden("traj_bigk256")
     ctx = capi.Context(big["D"])                      # 256 px: windowed above 64 stars

@@ -187,13 +187,19 @@ class _Oracle(RefModel):
         return RefModel.dphidq(self, q) * self.scale_G
 
 
+def _shape(name):
+    """A row of TABLE by its id; a row given itself (tests/test_gpu_ragged_bodies.py
+    builds its own rows' fields and oracle runs with the helpers below)."""
+    return TABLE[name] if isinstance(name, str) else name
+
+
 def _dt(K):
     return 0.1 if K <= 3 else 0.05 if K <= 16 else 0.02
 
 
 def _par(name, prior, f_lim, cap=False):
     """rhmc_params of one run (capi.make_params' keywords)."""
-    K, fwhm = TABLE[name][0], TABLE[name][5]
+    K, fwhm = _shape(name)[0], _shape(name)[5]
     par, _ = workloads.base_params(_dt(K) * (10. if cap else 1.), g_xx=0.05, g_ff=4., g_ff2=4.,
                                    use_prior=prior, alpha=2.)
     assert par["fwhm_pix"] == REF_FWHM
@@ -203,14 +209,14 @@ def _par(name, prior, f_lim, cap=False):
 
 
 def _model(name, D, par, scale_G=1.):
-    side = TABLE[name][1]
+    side = _shape(name)[1]
     return _Oracle(D, dict(par, rows=side, cols=side, fmin=-1., fmax=-1.), scale_G)
 
 
 def _start(name):
     """(D, q0, z) of a row.  One star on 96 / 128 px: three stars in the image,
     at both corners and mid-image, and the chains near them in turn."""
-    K, side, n, _, _, _, f32, _, _ = TABLE[name]
+    K, side, n, _, _, _, f32, _, _ = _shape(name)
     if K == 1 and side >= 96:
         _, _, ftc, fwhm, B, _, _, _ = default_exp_setup()
         rng = np.random.RandomState(100 + side)

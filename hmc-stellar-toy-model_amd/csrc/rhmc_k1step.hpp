@@ -92,6 +92,19 @@ __device__ __forceinline__ FluxMetric flux_metric(double f, const Consts& c,
   return m;
 }
 
+// The metric view of the explicit integrators (explicit_steps, rhmc_traj.hpp)
+// on the division-lean FluxMetric: p/H is p A (flux) and p s/g_xx (positions),
+// dVdq_RHMC's flux slot (:427-446) is p_f^2 coef/2 + mterm.
+struct LeanMetricView {
+  const FluxMetric& fm;
+  const LeanConsts& lc;
+  __device__ __forceinline__ double over_Hff(double v) const { return v * fm.A; }
+  __device__ __forceinline__ double over_Hxx(double v) const { return v * (fm.s * lc.inv_gxx); }
+  __device__ __forceinline__ double force_f(double p) const {
+    return (p * p) * fm.coef / 2.0 + fm.mterm;
+  }
+};
+
 // Lane-parallel q-loop passes (QL = 16 lanes per chain, one DPP row).
 __device__ __forceinline__ double row_shr1(double v) {  // lane l of a 16-lane row gets lane l - 1
   const long long b = __double_as_longlong(v);

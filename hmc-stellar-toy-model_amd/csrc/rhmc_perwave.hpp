@@ -651,15 +651,24 @@ struct EnergyArgs {
 //   HMC:        single_gym.run_single_HMC leapfrog, unit metric (:628-645)
 //   RHMC_NAIVE: run_single_RHMC solver="naive"     (:690-708)
 //   RHMC_LF:    run_single_RHMC solver="leap_frog" (:709-728)
-// The gradient at the end of a step is the next step's first one (same q).
-// dVdq_RHMC (:427-446): flux slot ((p_f^2 (-H_ff'/H_ff^2)) + H_ff'/H_ff + 2 H_xx'/H_xx)/2.
-__device__ __forceinline__ double dVdq_rhmc_f(double f, double pf, const Consts& c) {
-  const double hff = H_ff(f, c), hffg = H_ff_grad(f, c);
-  const double hxx = H_xx(f, c), hxxg = H_xx_grad(f, c);
-  const double t1 = (pf * pf) * (-hffg / (hff * hff));
-  const double t2 = (hffg / hff) + (2.0 * hxxg / hxx);
-  return (t1 + t2) / 2.0;
-}
+// The loop is explicit_steps (rhmc_traj.hpp); this family's metric view divides
+// by H_ff and H_xx at the slot's flux.
+struct WinMetricView {
+  // a copy, not a reference, on purpose: the drifts of x and y divide at the
+  // flux before the step's drift, after f[t] has already been updated
+  double f;
+  const Consts& c;
+  __device__ __forceinline__ double over_Hff(double v) const { return v / H_ff(f, c); }
+  __device__ __forceinline__ double over_Hxx(double v) const { return v / H_xx(f, c); }
+  // dVdq_RHMC (:427-446): flux slot ((p_f^2 (-H_ff'/H_ff^2)) + H_ff'/H_ff + 2 H_xx'/H_xx)/2.
+  __device__ __forceinline__ double force_f(double pf) const {
+    const double hff = H_ff(f, c), hffg = H_ff_grad(f, c);
+    const double hxx = H_xx(f, c), hxxg = H_xx_grad(f, c);
+    const double t1 = (pf * pf) * (-hffg / (hff * hff));
+    const double t2 = (hffg / hff) + (2.0 * hxxg / hxx);
+    return (t1 + t2) / 2.0;
+  }
+};
 
 template <class G, int SOLVER, int SLOTS>
 __global__ void __launch_bounds__(256) integrate_win_kernel(LeapArgs a, int f_pos) {
@@ -673,79 +682,22 @@ __global__ void __launch_bounds__(256) integrate_win_kernel(LeapArgs a, int f_po
   const LeanConsts lc = lean_consts(c);
   WinState<SLOTS> s;
   win_load<SLOTS>(a, chain, 3 * (int64_t)K, K, s);
-  const double dt = c.dt;
   unsigned st = 0u;
-  double gf[SLOTS], gx[SLOTS], gy[SLOTS];
-  // One gradient call site (the gradient is most of the kernel: a second
-  // copy is not inlined and its array arguments go to scratch).  Pass `step`
-  // closes step - 1 and opens step; the gradient at the end of a step is the
-  // next step's first one (same q).
-  for (int step = 0;; ++step) {
-    if (SOLVER == RHMC_SOLVER_RHMC_NAIVE && step == a.n_steps) break;
-    G::template gradient<SLOTS>(gctx, K, s.f, s.x, s.y, c, lc, false, gf, gx, gy);
-    if (SOLVER == RHMC_SOLVER_RHMC_NAIVE) {  // :690-708, the gradient at the step's start
+  explicit_steps<SOLVER, SLOTS>(
+      s.f, s.x, s.y, s.pf, s.px, s.py, a.n_steps, f_pos, c.f_lim, c.dt, st,
+      [&](double (&gf)[SLOTS], double (&gx)[SLOTS], double (&gy)[SLOTS]) RHMC_INLINE_LAMBDA {
+        G::template gradient<SLOTS>(gctx, K, s.f, s.x, s.y, c, lc, false, gf, gx, gy);
 #pragma unroll
-      for (int t = 0; t < SLOTS; ++t) {
-        const double hff = H_ff(s.f[t], c), hxx = H_xx(s.f[t], c);
-        const double nf = s.f[t] + dt * s.pf[t] / hff, nx = s.x[t] + dt * s.px[t] / hxx,
-                     ny = s.y[t] + dt * s.py[t] / hxx;
-        const double pf_old = s.pf[t];
-        s.pf[t] = s.pf[t] - dt * (gf[t] + dVdq_rhmc_f(s.f[t], s.pf[t], c));
-        s.px[t] = s.px[t] - dt * (gx[t] + 0.0);
-        s.py[t] = s.py[t] - dt * (gy[t] + 0.0);
-        if (f_pos && nf < c.f_lim) {
-          s.pf[t] = pf_old * -1.0;
-          if (s.own[t]) st |= RHMC_STATUS_REFLECT_F;
+        // + dVdq_RHMC's zero position slots, for every kick (HMC's first half
+        // kick once went without: that differs only in the sign of a zero, when
+        // the gradient and the momentum are both exactly -0.0)
+        for (int t = 0; t < SLOTS; ++t) {
+          gx[t] = gx[t] + 0.0;
+          gy[t] = gy[t] + 0.0;
         }
-        s.f[t] = nf;
-        s.x[t] = nx;
-        s.y[t] = ny;
-      }
-      continue;
-    }
-    if (step > 0) {  // second half kick of step - 1 (p holds the half-step momentum)
-#pragma unroll
-      for (int t = 0; t < SLOTS; ++t) {
-        if (SOLVER == RHMC_SOLVER_HMC) {  // :628-638
-          s.pf[t] = s.pf[t] - dt * gf[t] / 2.0;
-        } else {                          // :709-728
-          const double hf = s.pf[t];
-          s.pf[t] = hf - dt * (gf[t] + dVdq_rhmc_f(s.f[t], hf, c)) / 2.0;
-          if (f_pos && s.f[t] < c.f_lim) {
-            s.pf[t] = hf * -1.0;
-            if (s.own[t]) st |= RHMC_STATUS_REFLECT_F;
-          }
-        }
-        s.px[t] = s.px[t] - dt * (gx[t] + 0.0) / 2.0;
-        s.py[t] = s.py[t] - dt * (gy[t] + 0.0) / 2.0;
-      }
-    }
-    if (step == a.n_steps) break;
-#pragma unroll
-    for (int t = 0; t < SLOTS; ++t) {  // first half kick and drift of step
-      if (SOLVER == RHMC_SOLVER_HMC) {
-        const double hf = s.pf[t] - dt * gf[t] / 2.0, hx = s.px[t] - dt * gx[t] / 2.0,
-                     hy = s.py[t] - dt * gy[t] / 2.0;
-        s.f[t] = s.f[t] + dt * hf;
-        s.x[t] = s.x[t] + dt * hx;
-        s.y[t] = s.y[t] + dt * hy;
-        s.pf[t] = hf;
-        s.px[t] = hx;
-        s.py[t] = hy;
-      } else {
-        const double hff = H_ff(s.f[t], c), hxx = H_xx(s.f[t], c);
-        const double hf = s.pf[t] - dt * (gf[t] + dVdq_rhmc_f(s.f[t], s.pf[t], c)) / 2.0;
-        const double hx = s.px[t] - dt * (gx[t] + 0.0) / 2.0,
-                     hy = s.py[t] - dt * (gy[t] + 0.0) / 2.0;
-        s.f[t] = s.f[t] + dt * hf / hff;
-        s.x[t] = s.x[t] + dt * hx / hxx;
-        s.y[t] = s.y[t] + dt * hy / hxx;
-        s.pf[t] = hf;
-        s.px[t] = hx;
-        s.py[t] = hy;
-      }
-    }
-  }
+      },
+      [&](int t) RHMC_INLINE_LAMBDA { return WinMetricView{s.f[t], c}; },
+      [&](int t) RHMC_INLINE_LAMBDA { return s.own[t]; }, [] {});
   win_store<SLOTS>(a, chain, chain, 3 * (int64_t)K, K, s, 0, 0, st);
 }
 

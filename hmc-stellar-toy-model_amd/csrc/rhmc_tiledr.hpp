@@ -528,8 +528,9 @@ leapfrog_k1_tiledr(LeapArgsK1 a) {
 // :628-645), explicit RHMC naive (:690-708) and leap_frog (:709-728).
 // dVdq_RHMC's flux slot (:427-446), ((p_f^2 (-H_ff'/H_ff^2)) + H_ff'/H_ff +
 // 2 H_xx'/H_xx)/2, is p_f^2 coef/2 + mterm of the division-lean FluxMetric,
-// and p/H is p A (flux) / p s/g_xx (position).  The metric and gradient at
-// the end of a step are the next step's first ones (same q).
+// and p/H is p A (flux) / p s/g_xx (position): LeanMetricView.  The loop is
+// explicit_steps (rhmc_traj.hpp); the metric is taken before the gradient,
+// whose prior it carries.
 template <int IMG, int WIN, typename DT, int SOLVER>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
 integrate_k1_tiledr(LeapArgsK1 a, int f_pos) {
@@ -545,84 +546,33 @@ integrate_k1_tiledr(LeapArgsK1 a, int f_pos) {
   const bool real = chain < a.n_chains;            // ragged tail: mirror the wave's first chain
   const int64_t base = (real ? chain : TL::CPW * wave) * 3;
 
-  double f = a.q[base], x = a.q[base + 1], y = a.q[base + 2];
-  double pf = a.p[base], px = a.p[base + 1], py = a.p[base + 2];
+  double f[1] = {a.q[base]}, x[1] = {a.q[base + 1]}, y[1] = {a.q[base + 2]};
+  double pf[1] = {a.p[base]}, px[1] = {a.p[base + 1]}, py[1] = {a.p[base + 2]};
   const LeanConsts lc = lean_consts(c);
   typename TL::Cache cache;
   TL::init(cache);
-  const double dt = c.dt;
   unsigned st = 0u;
   FluxMetric fm{};
-  double gf, gx, gy;
-  auto grad = [&]() {                              // dVdq (:365-425)
-    TL::gradient(lds, simg, cache, f, x, y, c, lc, gf, gx, gy);
-    if (c.use_prior) gf += (SOLVER == RHMC_SOLVER_HMC) ? c.alpha / f : fm.prior;  // :408-409
-  };
-  auto dvdq_rhmc_f = [&](double p_f) { return (p_f * p_f) * fm.coef / 2.0 + fm.mterm; };
-  // One gradient call site: pass s closes step s - 1 and opens step s (p holds
-  // the half-step momentum across the gradient); naive's gradient opens its step.
-  for (int s = 0;; ++s) {
-    if constexpr (SOLVER != RHMC_SOLVER_HMC) fm = flux_metric(f, c, lc);
-    grad();
-    if (s > 0) {
-      if constexpr (SOLVER == RHMC_SOLVER_HMC) {   // :630-638
-        pf = pf - dt * gf / 2.0;
-      } else if constexpr (SOLVER == RHMC_SOLVER_RHMC_LEAPFROG) {  // :711-726
-        const double hf = pf;
-        pf = hf - dt * (gf + dvdq_rhmc_f(hf)) / 2.0;
-        if (f_pos && f < c.f_lim) {
-          pf = hf * -1.0;
-          st |= RHMC_STATUS_REFLECT_F;
-        }
-      }
-      if constexpr (SOLVER != RHMC_SOLVER_RHMC_NAIVE) {
-        px = px - dt * gx / 2.0;
-        py = py - dt * gy / 2.0;
-      }
-    }
-    if (s == a.n_steps) break;
-    if constexpr (SOLVER == RHMC_SOLVER_HMC) {
-      pf = pf - dt * gf / 2.0;
-      px = px - dt * gx / 2.0;
-      py = py - dt * gy / 2.0;
-      f = f + dt * pf;
-      x = x + dt * px;
-      y = y + dt * py;
-    } else if constexpr (SOLVER == RHMC_SOLVER_RHMC_NAIVE) {  // :692-705
-      const double ihxx = fm.s * lc.inv_gxx;
-      const double nf = f + (dt * pf) * fm.A, nx = x + (dt * px) * ihxx,
-                   ny = y + (dt * py) * ihxx;
-      const double pf_old = pf;
-      pf = pf - dt * (gf + dvdq_rhmc_f(pf));
-      px = px - dt * gx;
-      py = py - dt * gy;
-      if (f_pos && nf < c.f_lim) {
-        pf = pf_old * -1.0;
-        st |= RHMC_STATUS_REFLECT_F;
-      }
-      f = nf;
-      x = nx;
-      y = ny;
-    } else {
-      const double ihxx = fm.s * lc.inv_gxx;
-      pf = pf - dt * (gf + dvdq_rhmc_f(pf)) / 2.0;
-      px = px - dt * gx / 2.0;
-      py = py - dt * gy / 2.0;
-      f = f + (dt * pf) * fm.A;
-      x = x + (dt * px) * ihxx;
-      y = y + (dt * py) * ihxx;
-    }
-  }
+  explicit_steps<SOLVER, 1>(
+      f, x, y, pf, px, py, a.n_steps, f_pos, c.f_lim, c.dt, st,
+      [&](double (&gf)[1], double (&gx)[1], double (&gy)[1]) RHMC_INLINE_LAMBDA {
+        if constexpr (SOLVER != RHMC_SOLVER_HMC) fm = flux_metric(f[0], c, lc);
+        TL::gradient(lds, simg, cache, f[0], x[0], y[0], c, lc, gf[0], gx[0], gy[0]);  // :365-425
+        if (c.use_prior)                           // :408-409
+          gf[0] += (SOLVER == RHMC_SOLVER_HMC) ? c.alpha / f[0] : fm.prior;
+      },
+      [&](int) RHMC_INLINE_LAMBDA { return LeanMetricView{fm, lc}; },
+      [](int) RHMC_INLINE_LAMBDA { return true; }, [] {});
   if ((lane % TL::LPC) == 0 && real) {
-    if (!(isfinite(f) && isfinite(x) && isfinite(y) && isfinite(pf) && isfinite(px) &&
-          isfinite(py)))
+    if (!(isfinite(f[0]) && isfinite(x[0]) && isfinite(y[0]) && isfinite(pf[0]) &&
+          isfinite(px[0]) && isfinite(py[0])))
       st |= RHMC_STATUS_NONFINITE;
-    a.q[base] = f;
-    a.q[base + 1] = x;
-    a.q[base + 2] = y;
-    a.p[base] = pf;
-    a.p[base + 1] = px;
-    a.p[base + 2] = py;
+    a.q[base] = f[0];
+    a.q[base + 1] = x[0];
+    a.q[base + 2] = y[0];
+    a.p[base] = pf[0];
+    a.p[base + 1] = px[0];
+    a.p[base + 2] = py[0];
     if (a.status) a.status[chain] = (int32_t)st;
   }
 }

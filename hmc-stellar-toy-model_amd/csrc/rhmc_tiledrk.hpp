@@ -627,11 +627,13 @@ __device__ __forceinline__ void km_steps(double (&f)[SLOTS], double (&x)[SLOTS],
 
 // n_steps steps of single_gym's explicit integrators for
 // the chain's stars: plain HMC, unit metric (sampler_RHMC.py:628-645), explicit
-// RHMC naive (:690-708) and leap_frog (:709-728), flux wall under f_pos.
-// dVdq_RHMC's flux slot (:427-446) is p_f^2 coef/2 + mterm of the division-
-// lean FluxMetric; p/H is p A (flux) and p s/g_xx (positions).  The gradient
-// and metric at the end of a step are the next step's first ones; the metric
-// is recomputed after each gradient rather than held across it (km_steps).
+// RHMC naive (:690-708) and leap_frog (:709-728), flux wall under f_pos:
+// explicit_steps (rhmc_traj.hpp, the rule) with what the two register kernels
+// do their own way.  The state goes to the star table before the first
+// gradient and after every update of q and, under RELOAD, comes back from it
+// after the gradient.  The metric is the division-lean FluxMetric
+// (LeanMetricView), recomputed after each gradient rather than held across it
+// (km_steps).
 template <int SOLVER, int SLOTS, class GRAD, bool RELOAD = false>
 __device__ __forceinline__ void km_explicit_steps(double (&f)[SLOTS], double (&x)[SLOTS],
                                                   double (&y)[SLOTS], double (&pf)[SLOTS],
@@ -640,100 +642,34 @@ __device__ __forceinline__ void km_explicit_steps(double (&f)[SLOTS], double (&x
                                                   int n_steps, int f_pos, const Consts& c,
                                                   const LeanConsts& lc, GRAD grad,
                                                   unsigned& st) {
-  const double dt = c.dt;
   FluxMetric fm[SLOTS];
-  double gf[SLOTS], gx[SLOTS], gy[SLOTS];
-  auto metric = [&]() {
-#pragma unroll
-    for (int t = 0; t < SLOTS; ++t) {
-      double fr = f[t];
-      asm volatile("" : "+v"(fr));
-      fm[t] = flux_metric(fr, c, lc);
-    }
-  };
-  auto gradient = [&]() {  // dVdq (:365-425) at the published state
-    grad(x, y, gf, gx, gy);
-    if constexpr (RELOAD) kr_reload<SLOTS>(tab, f, x, y, own);
-#pragma unroll
-    for (int t = 0; t < SLOTS; ++t)
-      if (c.use_prior) gf[t] += c.alpha / f[t];     // :408-409
-    // leap_frog needs the metric at the new f right away; naive computes it
-    // at the start of its next step (fewer live registers at SLOTS = 2)
-    if constexpr (SOLVER == RHMC_SOLVER_RHMC_LEAPFROG) metric();
-  };
-  auto dvdq_rhmc_f = [&](int t, double p_f) {
-    return (p_f * p_f) * fm[t].coef / 2.0 + fm[t].mterm;
-  };
   kr_publish<SLOTS>(tab, f, x, y, own);
-  if constexpr (SOLVER == RHMC_SOLVER_RHMC_NAIVE) {  // :692-705
-    // the gradient opens each step (nothing of it lives across steps)
-    for (int s = 0; s < n_steps; ++s) {
-      gradient();
-      metric();
+  explicit_steps<SOLVER, SLOTS>(
+      f, x, y, pf, px, py, n_steps, f_pos, c.f_lim, c.dt, st,
+      [&](double (&gf)[SLOTS], double (&gx)[SLOTS], double (&gy)[SLOTS]) RHMC_INLINE_LAMBDA {
+        grad(x, y, gf, gx, gy);                    // dVdq (:365-425) at the published state
+        if constexpr (RELOAD) kr_reload<SLOTS>(tab, f, x, y, own);
 #pragma unroll
-      for (int t = 0; t < SLOTS; ++t) {
-        const double ihxx = fm[t].s * lc.inv_gxx;
-        const double nf = f[t] + (dt * pf[t]) * fm[t].A;
-        x[t] = x[t] + (dt * px[t]) * ihxx;
-        y[t] = y[t] + (dt * py[t]) * ihxx;
-        const double pf_old = pf[t];
-        pf[t] = pf[t] - dt * (gf[t] + dvdq_rhmc_f(t, pf[t]));
-        px[t] = px[t] - dt * gx[t];
-        py[t] = py[t] - dt * gy[t];
-        if (f_pos && nf < c.f_lim) {
-          pf[t] = pf_old * -1.0;
-          if (own[t]) st |= RHMC_STATUS_REFLECT_F;
-        }
-        f[t] = nf;
-      }
-      kr_publish<SLOTS>(tab, f, x, y, own);
-    }
-    return;
-  }
-  // HMC (:630-638) / leap_frog (:711-726): one gradient call site (code size:
-  // the gradient is most of the kernel), pass s closes step s - 1 and opens
-  // step s; p holds the half-step momentum across the gradient.
-  for (int s = 0;; ++s) {
-    gradient();
-    if (s > 0) {
+        for (int t = 0; t < SLOTS; ++t)
+          if (c.use_prior) gf[t] += c.alpha / f[t];  // :408-409
+        // Both RHMC solvers take the metric at the new f straight after the
+        // gradient, recomputed rather than kept live through it (km_steps: the
+        // asm hides f's value from CSE): leap_frog needs it right away for
+        // the closing kick, and naive's gradient opens its step, so for it
+        // this is the start of the step, with nothing of the metric live across
+        // steps (fewer live registers at SLOTS = 2).
+        if constexpr (SOLVER != RHMC_SOLVER_HMC) {
 #pragma unroll
-      for (int t = 0; t < SLOTS; ++t) {
-        if constexpr (SOLVER == RHMC_SOLVER_HMC) {
-          pf[t] = pf[t] - dt * gf[t] / 2.0;
-        } else {
-          const double hf = pf[t];
-          pf[t] = hf - dt * (gf[t] + dvdq_rhmc_f(t, hf)) / 2.0;
-          if (f_pos && f[t] < c.f_lim) {
-            pf[t] = hf * -1.0;
-            if (own[t]) st |= RHMC_STATUS_REFLECT_F;
+          for (int t = 0; t < SLOTS; ++t) {
+            double fr = f[t];
+            asm volatile("" : "+v"(fr));
+            fm[t] = flux_metric(fr, c, lc);
           }
         }
-        px[t] = px[t] - dt * gx[t] / 2.0;
-        py[t] = py[t] - dt * gy[t] / 2.0;
-      }
-    }
-    if (s == n_steps) break;
-#pragma unroll
-    for (int t = 0; t < SLOTS; ++t) {
-      if constexpr (SOLVER == RHMC_SOLVER_HMC) {
-        pf[t] = pf[t] - dt * gf[t] / 2.0;
-        px[t] = px[t] - dt * gx[t] / 2.0;
-        py[t] = py[t] - dt * gy[t] / 2.0;
-        f[t] = f[t] + dt * pf[t];
-        x[t] = x[t] + dt * px[t];
-        y[t] = y[t] + dt * py[t];
-      } else {
-        const double ihxx = fm[t].s * lc.inv_gxx;
-        pf[t] = pf[t] - dt * (gf[t] + dvdq_rhmc_f(t, pf[t])) / 2.0;
-        px[t] = px[t] - dt * gx[t] / 2.0;
-        py[t] = py[t] - dt * gy[t] / 2.0;
-        f[t] = f[t] + (dt * pf[t]) * fm[t].A;
-        x[t] = x[t] + (dt * px[t]) * ihxx;
-        y[t] = y[t] + (dt * py[t]) * ihxx;
-      }
-    }
-    kr_publish<SLOTS>(tab, f, x, y, own);
-  }
+      },
+      [&](int t) RHMC_INLINE_LAMBDA { return LeanMetricView{fm[t], lc}; },
+      [&](int t) RHMC_INLINE_LAMBDA { return own[t]; },
+      [&]() RHMC_INLINE_LAMBDA { kr_publish<SLOTS>(tab, f, x, y, own); });
 }
 
 // samplers.lightsource_gym.HMC_random's trajectory (samplers.py:519-552), or

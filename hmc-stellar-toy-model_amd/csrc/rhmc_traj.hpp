@@ -1,13 +1,16 @@
 // rhmc_traj.hpp — the random-length trajectory of samplers.lightsource_gym's
 // HMC_random (samplers.py:519-552) and RHMC_random_diag (:766-800), once for
-// every kernel family (random_trajectory), and RHMC_random's (:1016-1067,
-// hess_trajectory).  Included from rhmc_wave.hpp (DiagArgs, diag_force_f,
-// diag_drift).
+// every kernel family (random_trajectory), RHMC_random's (:1016-1067,
+// hess_trajectory), and single_gym's explicit integrators, once for every
+// kernel family (explicit_steps).  Included from rhmc_wave.hpp (DiagArgs,
+// diag_force_f, diag_drift).
 #pragma once
+
+#include "rhmc.h"
 
 namespace rhmc {
 
-// A lambda that the trajectory calls from more than one site: without the
+// A lambda that a shared loop calls from more than one site: without the
 // attribute a gradient wrapped in one is not inlined at 8 slots and its array
 // arguments go to scratch.
 #define RHMC_INLINE_LAMBDA __attribute__((always_inline))
@@ -108,6 +111,101 @@ __device__ __forceinline__ bool random_trajectory(double (&f)[SLOTS], double (&x
     }
   }
   return flip;
+}
+
+// n_steps steps of single_gym's explicit integrators for SLOTS stars per lane,
+// once for every kernel family: plain HMC, unit metric (sampler_RHMC.py
+// :628-645), explicit RHMC "naive" (:690-708) and "leap_frog" (:709-728), the
+// flux wall at f_lim under f_pos.  The gradient at the end of a step is the
+// next step's first one (same q).  A flip takes the momentum from before the
+// kick, and only a lane that owns the star sets RHMC_STATUS_REFLECT_F.
+// What a family does its own way comes in as callables:
+//   force(gf, gx, gy)  dVdq (:365-425) at the current f, x, y with the flux
+//                      prior where the family adds it, with whatever the family
+//                      does around the gradient, and the family's metric at
+//                      that state where metric(t) reads it
+//   metric(t)          slot t's metric at the state of the last force(), as a
+//                      view: over_Hff(v) = v / H_ff, over_Hxx(v) = v / H_xx and
+//                      force_f(p), dVdq_RHMC's flux slot (:427-446; its position
+//                      slots are 0).  Not called for HMC.
+//   own(t)             the lane has a star in slot t
+//   moved()            after every update of q
+template <int SOLVER, int SLOTS, class FORCE, class METRIC, class OWN, class MOVED>
+__device__ __forceinline__ void explicit_steps(double (&f)[SLOTS], double (&x)[SLOTS],
+                                               double (&y)[SLOTS], double (&pf)[SLOTS],
+                                               double (&px)[SLOTS], double (&py)[SLOTS],
+                                               int n_steps, int f_pos, double f_lim, double dt,
+                                               unsigned& st, FORCE force, METRIC metric, OWN own,
+                                               MOVED moved) {
+  double gf[SLOTS], gx[SLOTS], gy[SLOTS];
+  if constexpr (SOLVER == RHMC_SOLVER_RHMC_NAIVE) {
+    // the gradient opens each step (nothing of it lives across steps)
+    for (int s = 0; s < n_steps; ++s) {
+      force(gf, gx, gy);
+#pragma unroll
+      for (int t = 0; t < SLOTS; ++t) {
+        const auto m = metric(t);
+        const double nf = f[t] + m.over_Hff(dt * pf[t]);       // :692
+        x[t] = x[t] + m.over_Hxx(dt * px[t]);
+        y[t] = y[t] + m.over_Hxx(dt * py[t]);
+        const double pf_old = pf[t];
+        pf[t] = pf[t] - dt * (gf[t] + m.force_f(pf[t]));       // :696
+        px[t] = px[t] - dt * gx[t];
+        py[t] = py[t] - dt * gy[t];
+        if (f_pos && nf < f_lim) {                             // :698-704, the new flux
+          pf[t] = pf_old * -1.0;
+          if (own(t)) st |= RHMC_STATUS_REFLECT_F;
+        }
+        f[t] = nf;
+      }
+      moved();
+    }
+  } else {
+    // One gradient call site (the gradient is most of a kernel): pass s closes
+    // step s - 1 and opens step s; p holds the half-step momentum across the
+    // gradient.
+    for (int s = 0;; ++s) {
+      force(gf, gx, gy);
+      if (s > 0) {                                             // second half kick of step s - 1
+#pragma unroll
+        for (int t = 0; t < SLOTS; ++t) {
+          if constexpr (SOLVER == RHMC_SOLVER_HMC) {           // :638
+            pf[t] = pf[t] - dt * gf[t] / 2.0;
+          } else {                                             // :717-725
+            const double hf = pf[t];
+            pf[t] = hf - dt * (gf[t] + metric(t).force_f(hf)) / 2.0;
+            if (f_pos && f[t] < f_lim) {                       // the flux of this gradient
+              pf[t] = hf * -1.0;
+              if (own(t)) st |= RHMC_STATUS_REFLECT_F;
+            }
+          }
+          px[t] = px[t] - dt * gx[t] / 2.0;
+          py[t] = py[t] - dt * gy[t] / 2.0;
+        }
+      }
+      if (s == n_steps) break;
+#pragma unroll
+      for (int t = 0; t < SLOTS; ++t) {                        // first half kick and drift of step s
+        if constexpr (SOLVER == RHMC_SOLVER_HMC) {             // :631-634
+          pf[t] = pf[t] - dt * gf[t] / 2.0;
+          px[t] = px[t] - dt * gx[t] / 2.0;
+          py[t] = py[t] - dt * gy[t] / 2.0;
+          f[t] = f[t] + dt * pf[t];
+          x[t] = x[t] + dt * px[t];
+          y[t] = y[t] + dt * py[t];
+        } else {                                               // :711-714
+          const auto m = metric(t);
+          pf[t] = pf[t] - dt * (gf[t] + m.force_f(pf[t])) / 2.0;
+          px[t] = px[t] - dt * gx[t] / 2.0;
+          py[t] = py[t] - dt * gy[t] / 2.0;
+          f[t] = f[t] + m.over_Hff(dt * pf[t]);
+          x[t] = x[t] + m.over_Hxx(dt * px[t]);
+          y[t] = y[t] + m.over_Hxx(dt * py[t]);
+        }
+      }
+      moved();
+    }
+  }
 }
 
 // One star's derivative sets of RHMC_efficient_computation (samplers.py:881-903):

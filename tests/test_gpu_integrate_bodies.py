@@ -2,11 +2,12 @@
 
 rhmc_integrate with RHMC_SOLVER_HMC, _RHMC_NAIVE or _RHMC_LEAPFROG launches one
 of 25 kernel bodies (csrc/rhmc_launch.hpp: launch_integrate), each built once
-per solver, around three copies of the integrator loop: integrate_k1_tiledr
-(one star), km_explicit_steps (multi-star register window and pixel-major) and
-integrate_win_kernel (windowed and dense).  TABLE takes the shapes of
-test_gpu_traj_bodies.TABLE, at least one per body with the body's key beside
-it, and adds a step size and a step count per row;
+per solver, around one integrator loop (explicit_steps, csrc/rhmc_traj.hpp)
+and three adapters that supply the gradient, the metric and the star table:
+integrate_k1_tiledr (one star), km_explicit_steps (multi-star register window
+and pixel-major) and integrate_win_kernel (windowed and dense).  TABLE takes
+the shapes of test_gpu_traj_bodies.TABLE, at least one per body with the body's
+key beside it, and adds a step size and a step count per row;
 tests/test_integrate_bodies.py checks on the CPU (tests/native/traj_bodies.cpp
 in its `integrate` mode, which asks csrc/rhmc_select.hpp and the launchers' own
 csrc/rhmc_dispatch.hpp) that every shape is served by the body written here and

@@ -1,5 +1,6 @@
 """The explicit integrators on the one-star register-
-window kernel (integrate_k1_tiledr, rhmc_tiledr.hpp) through the C-ABI
+window kernel (integrate_k1_tiledr, rhmc_tiledr.hpp: the one-star adapter of
+the shared loop explicit_steps, rhmc_traj.hpp) through the C-ABI
 rhmc_integrate, at the bench's C2 geometry:
 
 * oracle sample: chains of the full 4096-chain launch match oracle/rhmc_ref's

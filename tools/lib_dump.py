@@ -16,8 +16,16 @@ comparison of the LDS-image bodies (ldsimage/MAXK) passes --kernel generic.
 --op hmc_random / diag_random: the trajectories of a KxSIDE field built as
 tools/diag_bench.py builds it, with unequal lengths of at most 40 steps; q, p,
 status and, for diag_random with --trace, the trace.  --wall puts a flux wall
-just under every chain's faintest star and sends that star towards it.
-  python tools/lib_dump.py 3x48 out.npz --op diag_random --kernel multiwin --chains 5"""
+just under the star that is faintest in chain 0, in every chain, and sends that
+star towards it.
+  python tools/lib_dump.py 3x48 out.npz --op diag_random --kernel multiwin --chains 5
+--op integrate: --steps (default 10) steps of the explicit integrator --solver
+(hmc, naive or leap_frog) at the step --dt on the KxSIDE field of the leapfrog
+op, unit-normal momenta for hmc; q, p and status.  --wall turns f_pos on, puts
+the wall at half the faintest flux of the field and, in every chain, starts the
+star that is faintest in chain 0 just above it, moving down (hmc crosses the
+wall too, which it never tests: its status must stay 0).
+  python tools/lib_dump.py 70x32 out.npz --op integrate --solver naive --wall --steps 9"""
 import argparse
 import os
 import re
@@ -34,16 +42,19 @@ ap = argparse.ArgumentParser()
 ap.add_argument("workload", help="a workload name (leapfrog) or KxSIDE (trajectories)")
 ap.add_argument("out")
 ap.add_argument("--op", default="leapfrog",
-                choices=["leapfrog", "energy", "gradient", "hmc_random", "diag_random"])
+                choices=["leapfrog", "energy", "gradient", "hmc_random", "diag_random",
+                         "integrate"])
+ap.add_argument("--solver", default="leap_frog", choices=["hmc", "naive", "leap_frog"],
+                help="integrate: the explicit integrator")
 ap.add_argument("--kernel", default="auto", help="kernel family (capi.KERNELS)")
 ap.add_argument("--chains", type=int, default=None)
-ap.add_argument("--dt", type=float, default=None, help="trajectories: the step (diag_bench's)")
+ap.add_argument("--dt", type=float, default=None, help="trajectories: the step (diag_bench's); integrate: dt")
 ap.add_argument("--trace", action="store_true", help="diag_random: save the trace too")
-ap.add_argument("--wall", action="store_true", help="trajectories: a flux wall that chains cross")
+ap.add_argument("--wall", action="store_true", help="trajectories, integrate: a flux wall that chains cross")
 ap.add_argument("--no-prior", action="store_true", help="KxSIDE: the flux prior off")
 ap.add_argument("--vc", action="store_true", help="KxSIDE: the pair potential on")
 ap.add_argument("--fwhm", type=float, default=None, help="KxSIDE: the PSF's FWHM in px")
-ap.add_argument("--steps", type=int, default=None, help="leapfrog: steps of the launch")
+ap.add_argument("--steps", type=int, default=None, help="leapfrog, integrate: steps of the launch")
 ap.add_argument("--inexact", action="store_true", help="KxSIDE: D + 0.1, not exact in fp32")
 ap.add_argument("--f-pos", type=int, default=0, help="energy: rhmc_energy's f_pos bits")
 ap.add_argument("--no-T", action="store_true", help="energy: V alone (no momenta)")
@@ -108,6 +119,35 @@ def gradient(args):
     print("gradient %s %s: %d chains -> %s" % (args.workload, args.kernel, wl.n_chains, args.out))
 
 
+def integrate(args):
+    wl = workload(args)
+    par, n, n_steps = wl.params, wl.n_chains, 10 if args.steps is None else args.steps
+    if args.dt:
+        par["dt"] = args.dt
+    hmc = args.solver == "hmc"
+    q0 = wl.q0.copy()
+    p0 = wl.p0 / np.sqrt(workloads.metric_diag(q0, par)) if hmc else wl.p0.copy()
+    if args.wall:   # the faintest star starts just above the wall, moving down
+        par["f_lim"] = 0.5 * q0[:, 0::3].min()
+        faint = 3 * int(np.argmin(q0[0, 0::3]))
+        q0[:, faint] = par["f_lim"] * (1.002 + 0.002 * np.arange(n))
+        if hmc:     # unit metric: the momentum that carries it as far below, were it free
+            p0[:, faint] = -2. * (q0[:, faint] - par["f_lim"]) / (par["dt"] * max(n_steps, 1))
+        else:
+            p0[:, faint] = (-2.0 - 0.1 * np.arange(n)) * np.sqrt(
+                workloads.metric_diag(q0, par)[:, faint])
+    ctx = capi.Context(wl.D, device=0, kernel=args.kernel)
+    solver = {"hmc": capi.SOLVER_HMC, "naive": capi.SOLVER_RHMC_NAIVE,
+              "leap_frog": capi.SOLVER_RHMC_LEAPFROG}[args.solver]
+    q, p, st = ctx.integrate(capi.make_params(**par), solver, q0, p0, n_steps, f_pos=args.wall,
+                             return_status=True)
+    np.savez(args.out, q=q, p=p, st=st)
+    print("integrate %s %s %s: %d chains x %d steps, %d chains with REFLECT_F, %d non-finite -> %s"
+          % (args.solver, args.workload, args.kernel, n, n_steps,
+             int((st & capi.STATUS_REFLECT_F != 0).sum()),
+             int((st & capi.STATUS_NONFINITE != 0).sum()), args.out))
+
+
 def trajectories(args):
     import diag_bench
     from rhmc_amd.photometry import mag2flux
@@ -145,7 +185,8 @@ def trajectories(args):
 
 def main(argv=None):
     args = ap.parse_args(argv)
-    {"leapfrog": leapfrog, "energy": energy, "gradient": gradient}.get(args.op, trajectories)(args)
+    {"leapfrog": leapfrog, "energy": energy, "gradient": gradient,
+     "integrate": integrate}.get(args.op, trajectories)(args)
 
 
 if __name__ == "__main__":
